@@ -6,8 +6,8 @@ MPC QPs per GPU, N=100, nx=12, nu=4 (nb = 4 / 10 / 6 on stage 0 / inner / N), fp
 stage data (no aliased buffers), solved by the residual-based Mehrotra IPM
 (d_ip2_res_mpc_hard_tv: mu0=2, mu_tol=1e-12, alpha_min=1e-8, k_max=50).
 
-A "step" is one batch of 1024 problems (default K = 20 steps, the driver's count; the same line reports K = 40 in
-"k40").  The K timed steps are solved through one problem queue (hpmpc_mi355x_ipm_queue): 8 x 1024 resident solver
+A "step" is one batch of 1024 problems (default K = 20 steps, the driver's count; with --full the same line reports
+K = 40 in "k40").  The K timed steps are solved through one problem queue (hpmpc_mi355x_ipm_queue): 8 x 1024 resident solver
 slots in four lanes of 2048 on four streams, each slot taking the next problem (one shared counter) as soon as its
 own has converged (iterations are ticks of the pass kernels hk_ipm_fact, hk_ipm_pred, hk_ipm_corr, hk_ipm_update over
 a lane's slots; once the queue is empty and few slots still iterate, they finish on the multi-wave kernel
@@ -15,6 +15,11 @@ hk_ipm_qdrain_mw).  value = IP iterations per second over all ranks (sum of per-
 max-over-ranks time).  The lanes run the four passes concurrently, so the roofline's unit of work is one step (all
 four passes' algorithmic bytes over the step's IP iterations, over the step's wall time); the dominant pass's
 per-launch figures (hipEvents at every kernel boundary inside the timed region) and `per_pass` are kept beside it.
+
+A plain run (`--gpus 1 --steps K --warmup W`) measures the headline only: set-up, the warm-up queue, the K timed
+steps, the files of --dump-outputs, and the result line (the other legs' keys are null).  Everything below runs
+with --full.
+
 An isolated single-batch solve is reported beside it.
 The Riccati factorisation rate (d_back_ric_rec_sv_tv_res, nb = 0, compute_pi = 1) of the same
 batch is reported in the same JSON line, and so is configs[4] ("pcond": 512 x N=200 nx=24 nu=6 condensed into
@@ -77,7 +82,19 @@ def parse():
     ap.add_argument("--no-coupled", action="store_true", help="skip the coupled-Hessian IPM leg")
     ap.add_argument("--check-launch", action="store_true", help="start the ranks, join the process group (gloo) "
                     "and print each rank's world size, without touching the GPU (launcher test)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the headline queue run, also run every other leg (k40, "
+                    "queue_batch_slots, generic_shape, isolated_batch, aliased, coupled, riccati, cpu_baseline, "
+                    "scatter, pcond, riccati_batch_N50, single_qp) and the parity samples against the reference "
+                    "build; the --no-* options drop single legs of it.  Without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the queue "
+                    "returned for the converged entries of the last step's batch (rank 0's) as DIR/<name>.npy, float64: "
+                    "ux, pi, lam, t, kk, ret, entries (the queue entries the rows belong to) and ret_batch (the ret of "
+                    "every entry of the step); see dump_outputs")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_k40 = args.no_cpu = args.no_pcond = args.no_isolated = args.no_scatter = True
+        args.no_queue_batch_slots = args.no_aliased = args.no_coupled = True
+    return args
 
 
 def launch_ranks(args):
@@ -192,6 +209,49 @@ def parity_sv(ref, qp, ux_t, pi_t, problems, compute_pi=1):
 def spread(n, total):
     """n indices spread over [0, total)."""
     return sorted({int(round(x)) for x in np.linspace(0, total - 1, n)})
+
+
+DUMP_MAX_BYTES = 60e6  # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_outputs(path, qp, Q, steps):
+    """--dump-outputs: what the timed queue returned for its last step (the entries (steps - 1) * B ... steps * B - 1,
+    entry q solving problem q % B), as float64 .npy files: ux, pi, lam, t in the queue's own padded layout
+    (entry, stage, column) with the columns past a stage's sizes set to 0 (the library leaves them unspecified;
+    the valid ones are parity_ipm's), kk, ret, and `entries`, the queue entry of every row.  A batch whose arrays would
+    exceed DUMP_MAX_BYTES is written as a fixed sample of its entries (PCG64(0), sorted).
+
+    Rows are the sample's converged entries (ret == 0).  An entry that stops on k_max or alpha_min (ret 1 / 2; ~10 % of
+    this workload's draws are box-infeasible) ends on whichever kernel the host's polling leaves it to -- the pass
+    kernels or the multi-wave drain, which round differently -- and its diverging iterate (|lam| up to 1e39) amplifies
+    that, so its arrays and its kk differ from run to run of one build; ret does not, and `ret_batch` holds the ret
+    of every entry of the step.  The converged entries were bitwise equal over runs with and without the drain."""
+    B, N = qp.batch, qp.N
+    per_entry = 8 * ((N + 1) * (Q.ux.shape[2] + Q.pi.shape[2] + Q.lam.shape[2] + Q.t.shape[2]) + 3)
+    n = int(min(B, DUMP_MAX_BYTES // per_entry))
+    rows = np.arange(B) if n == B else np.sort(np.random.Generator(np.random.PCG64(0)).choice(B, n, replace=False))
+    ret = Q.ret[(steps - 1) * B:].cpu().numpy()
+    rows = rows[ret[rows] == 0] + (steps - 1) * B
+    sel = Q.kk.new_tensor(rows).long()
+    m_ux = np.zeros((N + 1, Q.ux.shape[2]), dtype=bool)
+    m_pi = np.zeros((N + 1, Q.pi.shape[2]), dtype=bool)
+    m_lt = np.zeros((N + 1, Q.lam.shape[2]), dtype=bool)
+    for k in range(N + 1):
+        m_ux[k, :qp.nux(k)] = True
+        if k < N:
+            m_pi[k, :int(qp.nx[k + 1])] = True
+        nb, pnb = int(qp.nb[k]), qp.pnb(k)
+        m_lt[k, :nb] = True
+        m_lt[k, pnb:pnb + nb] = True
+    os.makedirs(path, exist_ok=True)
+    for name, t, mask in (("ux", Q.ux, m_ux), ("pi", Q.pi, m_pi), ("lam", Q.lam, m_lt), ("t", Q.t, m_lt),
+                          ("kk", Q.kk, None), ("ret", Q.ret, None)):
+        a = t[sel].cpu().numpy().astype(np.float64)
+        if mask is not None:
+            a = np.where(mask[None], a, 0.0)
+        np.save(os.path.join(path, name + ".npy"), a)
+    np.save(os.path.join(path, "entries.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "ret_batch.npy"), ret.astype(np.float64))
 
 
 def cpu_baseline(qp, seconds, k_max, threads):
@@ -689,6 +749,43 @@ def bench_riccati_small(args, torch, red, rank, world, barrier, stream):
                                     "frac": B * by / (ms1 * 1e-3) / 1e9 / PEAK_HBM_GBS}}
 
 
+def bench_riccati(args, torch, red, rank, world, barrier, B, ref):
+    """The Riccati factorisation + solve rate (d_back_ric_rec_sv_tv_res, nb = 0, compute_pi = 1) of the headline's
+    batch shape: the "riccati" entry of the line."""
+    from hpmpc_amd.batch import BatchSolver, algorithmic_bytes_per_sv, flops_sv
+    from hpmpc_amd.shard import make_shard
+
+    N, nx, nu = args.N, args.nx, args.nu
+    qp_ric = make_shard(N, nx, nu, rank, world, B, boxes=False)
+    # K steps of one batch each with args.sv_streams batches in flight (own output buffers per stream), and the same
+    # K steps on one stream beside it
+    rics = [BatchSolver(qp_ric, k_max=1) for _ in range(max(args.sv_streams, 1))]
+    for _ in range(args.warmup):
+        for r_ in rics:
+            r_.ric_sv()
+    rdt1, sv_ms1 = sv_timed(torch, rics[:1], args.steps, barrier, red)
+    rdt, sv_ms = sv_timed(torch, rics, args.steps, barrier, red)
+    sv_ms = sv_ms1 if sv_ms is None else sv_ms
+    fact_total = B * world * args.steps
+    par_sv = None
+    if ref is not None:
+        ps = [parity_sv(ref, qp_ric, r_.ux, r_.pi, spread(8, B)) for r_ in rics]
+        par_sv = max(ps, key=lambda x: x["max_rel_err"]) if all(ps) else None
+    sv_bytes = algorithmic_bytes_per_sv(qp_ric)
+    sv_achieved = B * args.steps * sv_bytes / rdt / 1e9  # this rank's launches over the (max-over-ranks) wall time
+    return {"value": fact_total / rdt, "unit": "fact/s", "kernel": "hk_ric_sv", "launch_ms": sv_ms,
+            "batches_in_flight": len(rics), "parity": par_sv,
+            "roofline": {"bound": "hbm", "achieved": sv_achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                         "frac": sv_achieved / PEAK_HBM_GBS,
+                         "algorithmic_bytes_per_sv": sv_bytes,
+                         "unit_of_work": f"K = {args.steps} launches of one batch, {len(rics)} in flight, "
+                                         "over their wall time (the launches overlap; launch_ms is the "
+                                         "one-stream run's per-launch time)",
+                         "fp64_tflops": B * args.steps * flops_sv(N, nx, nu) / rdt / 1e12},
+            "one_batch_in_flight": {"value": fact_total / rdt1, "launch_ms": sv_ms1,
+                                    "frac": B * sv_bytes / (sv_ms1 * 1e-3) / 1e9 / PEAK_HBM_GBS}}
+
+
 def bench_aliased(args, torch, red, rank, world, barrier, slots):
     """SURVEY.md §8d's aliased "time-invariant" mode, reported beside the headline: the same IPM workload, but every
     problem shares one A / B / Q / R (time-invariant mass-spring data, the drivers' aliasing, test_d_ip_hard.c:652-662)
@@ -837,7 +934,7 @@ def main():
     print(f"bench.py: rank {rank} of world {world} on cuda:{local}", file=sys.stderr, flush=True)
 
     from hpmpc_amd.batch import (BatchSolver, IpmQueue, algorithmic_bytes_per_ip_iter, algorithmic_bytes_per_pass,
-                                 algorithmic_bytes_per_sv, flops_ip_iter, flops_sv)
+                                 flops_ip_iter)
     from hpmpc_amd.shard import Reducer, make_shard
 
     from hpmpc_amd.shard import split_batch
@@ -848,8 +945,6 @@ def main():
         B = split_batch(args.global_batch, world)
     qp = make_shard(N, nx, nu, rank, world, B)
     solver = BatchSolver(qp, k_max=args.k_max)
-    qp_ric = make_shard(N, nx, nu, rank, world, B, boxes=False)
-    ric = BatchSolver(qp_ric, k_max=1)
     stream = torch.cuda.current_stream()
     red = Reducer(dist, "cuda")
     solver._red = red
@@ -918,10 +1013,12 @@ def main():
     n_lanes = len(Q.lanes())
     fl_iter = flops_ip_iter(N, nx, nu)
     # parity sample of the timed run (after it): 8 queue entries spread over the K batches against the reference
-    ref = ref_api() if rank == 0 else None
+    ref = ref_api() if (args.full and rank == 0) else None
     nq = args.steps * B
     par_ipm = parity_ipm(ref, qp, dict(ux=Q.ux, pi=Q.pi, lam=Q.lam, t=Q.t, kk=Q.kk, ret=Q.ret, k_max=args.k_max),
                          [(q, q % B) for q in spread(8, nq)])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, qp, Q, args.steps)
     del Q
 
     # the same queue with 40 batches (the drain's fixed cost amortised over twice the work), beside the driver's K
@@ -1009,23 +1106,7 @@ def main():
     ali = None if args.no_aliased else bench_aliased(args, torch, red, rank, world, barrier, slots)
     cpl = None if args.no_coupled else bench_coupled(args, torch, red, rank, world, barrier, slots, value)
 
-    # ---------------- Riccati factorisation + solve ----------------
-    # K steps of one batch each with args.sv_streams batches in flight (own output buffers per stream), and the same
-    # K steps on one stream beside it
-    rics = [ric] + [BatchSolver(qp_ric, k_max=1) for _ in range(max(args.sv_streams, 1) - 1)]
-    for _ in range(args.warmup):
-        for r_ in rics:
-            r_.ric_sv()
-    rdt1, sv_ms1 = sv_timed(torch, rics[:1], args.steps, barrier, red)
-    rdt, sv_ms = sv_timed(torch, rics, args.steps, barrier, red)
-    sv_ms = sv_ms1 if sv_ms is None else sv_ms
-    fact_total = B * world * args.steps
-    par_sv = None
-    if ref is not None:
-        ps = [parity_sv(ref, qp_ric, r_.ux, r_.pi, spread(8, B)) for r_ in rics]
-        par_sv = max(ps, key=lambda x: x["max_rel_err"]) if all(ps) else None
-    sv_bytes = algorithmic_bytes_per_sv(qp_ric)
-    sv_achieved = B * args.steps * sv_bytes / rdt / 1e9  # this rank's launches over the (max-over-ranks) wall time
+    rc_ = bench_riccati(args, torch, red, rank, world, barrier, B, ref) if args.full else None
 
     traffic = traffic_dom_launch = None
     pmc = os.path.join(ROOT, "profiles", "pmc_hk_ipm.json")
@@ -1130,17 +1211,7 @@ def main():
             "isolated_batch": iso,
             "scatter": sc,
             "parity": par_ipm,
-            "riccati": {"value": fact_total / rdt, "unit": "fact/s", "kernel": "hk_ric_sv", "launch_ms": sv_ms,
-                        "batches_in_flight": len(rics), "parity": par_sv,
-                        "roofline": {"bound": "hbm", "achieved": sv_achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                     "frac": sv_achieved / PEAK_HBM_GBS,
-                                     "algorithmic_bytes_per_sv": sv_bytes,
-                                     "unit_of_work": f"K = {args.steps} launches of one batch, {len(rics)} in flight, "
-                                                     "over their wall time (the launches overlap; launch_ms is the "
-                                                     "one-stream run's per-launch time)",
-                                     "fp64_tflops": B * args.steps * flops_sv(N, nx, nu) / rdt / 1e12},
-                        "one_batch_in_flight": {"value": fact_total / rdt1, "launch_ms": sv_ms1,
-                                                "frac": B * sv_bytes / (sv_ms1 * 1e-3) / 1e9 / PEAK_HBM_GBS}},
+            "riccati": rc_,
             "cpu_baseline": cpu,
             "pcond": pc,
             "riccati_batch_N50": rs,

@@ -24,7 +24,7 @@ for i in 1 2 3; do
     fi
     iso=--no-isolated
     [ "$mode" = ric ] && iso=  # the Riccati legs: configs[2] (riccati_batch_N50) runs with the isolated legs
-    HPMPC_MI355X_LIB=$PWD/hpmpc_amd/lib/ab/lib$v.so timeout -k 10 300 python3 bench.py --no-cpu --no-pcond $iso \
+    HPMPC_MI355X_LIB=$PWD/hpmpc_amd/lib/ab/lib$v.so timeout -k 10 300 python3 bench.py --full --no-cpu --no-pcond $iso \
       --no-queue-batch-slots --no-aliased --steps 20 > gpurun_out/ab/$v$i.log 2>&1 || { tail -20 gpurun_out/ab/$v$i.log; exit 1; }
     python3 - "$v$i" <<'PY'
 import json, sys

@@ -14,7 +14,7 @@ step pmc bash tools/pmc_mix.sh
 cp gpurun_out/pmc_hk_ipm.json profiles/pmc_hk_ipm.json && cp gpurun_out/pmc_mix.json gpurun_out/${R}_pmc_mix.json
 step hbmbw timeout -k 10 120 python3 tools/hbm_bw.py
 grep '^{' gpurun_out/hbmbw.log | tail -1 > gpurun_out/${R}_hbm_bw.json
-step bench timeout -k 10 600 python3 bench.py
+step bench timeout -k 10 600 python3 bench.py --full
 grep '^{' gpurun_out/bench.log | tail -1 > gpurun_out/${R}_bench.json
 # kernel stats of the timed region only: no warmup queue, no isolated batch, so every hk_ipm_* launch
 # in the trace is one of the timed queue's (its average matches the bench line's launch_ms)
