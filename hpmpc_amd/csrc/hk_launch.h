@@ -1,0 +1,27 @@
+// hk_launch.h -- the launch functions the kernel translation units (*.hip) define and the host C-ABI files call.
+// extern "C" names are not mangled, so a prototype repeated by hand at a call site would still link after its
+// signature drifted; every definer and every caller includes this header instead, and a mismatch is a compile
+// error.  The launch ids (`which`) are the enums next to each argument block (hpmpc_kargs.h, hk_soft_args.h,
+// hk_wide_args.h).  Return: 0, a hipError_t, -1 for an unknown id, or HK_LAUNCH_REFUSED (hk_launch_guard.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+struct KArgs;
+struct SoftArgs;
+struct SoftResArgs;
+struct WideIpmArgs;
+
+extern "C" {
+// hpmpc_kernels.hip: the tile kernels (which: HkLaunch) and the compiled inner-stage class of a stage size
+int hk_launch(int which, const KArgs* a, int count, hipStream_t stream);
+int hk_fixcls(int nu, int nx);
+#ifdef HK_RIC2  // the two-wave sv (hk_ric2.hip), a measured negative result: only in the ric2 build variant
+int hk_launch_ric2(int which, const KArgs* a, int count, hipStream_t stream);
+#endif
+// hk_soft.hip: the soft-constraint IPM passes (which: HkSoftPass) and the soft residual
+int hk_soft_launch(int which, const SoftArgs* a, int count, hipStream_t stream);
+int hk_soft_res_launch(const SoftResArgs* a, hipStream_t stream);
+// hk_wide.hip (which: HkWideLaunch; args: the WideArgs / PcArgs / PxArgs of that kernel) and hk_wide_ipm.hip
+int hk_wide_launch(int which, const void* args, int count, int lds_doubles, hipStream_t stream);
+int hk_wide_ipm_launch(const WideIpmArgs* a, int count, int lds_doubles, hipStream_t stream);
+}

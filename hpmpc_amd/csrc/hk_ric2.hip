@@ -26,6 +26,7 @@
 // are complete, wave 1's prefetched loads stay in flight across it.  Every slot's reuse is ordered by a barrier (the
 // comments at each ring say which).
 #include "hk_mw.h"
+#include "hk_launch.h"
 #include "hk_launch_guard.h"
 #include "hpmpc_kargs.h"
 
@@ -457,11 +458,11 @@ static int launch2_t(const KArgs* a, int count, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-// which: 0 = d_back_ric_rec_sv_tv_res (the only entry point with a two-wave kernel).  HK_LAUNCH_REFUSED: the caller
+// which: K_SV = d_back_ric_rec_sv_tv_res (the only entry point with a two-wave kernel).  HK_LAUNCH_REFUSED: the caller
 // runs the one-wave kernel instead.
 extern "C" int hk_launch_ric2(int which, const KArgs* a, int count, hipStream_t stream) {
     if (count <= 0) return 0;
-    if (which != 0) return HK_LAUNCH_REFUSED;
+    if (which != K_SV) return HK_LAUNCH_REFUSED;
     switch (a->fixcls) {
         case 1: return launch2_t<FixSh<4, 12>>(a, count, stream);
         case 2: return launch2_t<FixSh<3, 8>>(a, count, stream);

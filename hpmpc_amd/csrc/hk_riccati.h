@@ -16,6 +16,7 @@
 #pragma once
 
 #include "hk_prims.h"
+#include "hpmpc_kargs.h"
 
 namespace hk {
 
@@ -33,9 +34,9 @@ struct StageInfo {
     int oG;             // offset (doubles) of DCt_k inside one problem's general-constraint array
 };
 
-constexpr int FSTRIDE = 352;  // factor doubles per stage: 4 regs x 64 lanes + l (16) + inv_diag (16) + KG (64)
-constexpr int V16 = 16;       // per-stage stride of tile/state vectors
-constexpr int V32 = 32;       // per-stage stride of constraint vectors ([lb | pad | ub | pad])
+using ::FSTRIDE;  // the per-stage strides (hpmpc_kargs.h, shared with the host)
+using ::V16;
+using ::V32;
 
 __device__ __forceinline__ bool tile_active(int t, int nu, int nx, int xo) {
     return t < nu || (t >= xo && t < xo + nx);

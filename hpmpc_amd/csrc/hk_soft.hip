@@ -13,15 +13,15 @@
 // loop has ended, so a batch can run a fixed number of iterations without host round trips.
 #include <hip/hip_runtime.h>
 
+#include "hk_launch.h"
 #include "hk_prims.h"
 #include "hk_soft_args.h"
+#include "hpmpc_kargs.h"
 
 namespace {
 
 using hk::wave_min;
 using hk::wave_sum;
-
-constexpr int V16 = 16;
 
 struct Lane {
     int k, c;
@@ -134,14 +134,14 @@ __device__ double soft_alpha(const SoftArgs& a, const Prob& P) {
 
 }  // namespace
 
-// which: 0 init, 1 hess, 2 pred, 3 corr
+// which: HkSoftPass
 __global__ __launch_bounds__(64) void hk_soft_pass(SoftArgs a, int which) {
     const int p = blockIdx.x + a.p0;
     if (p >= a.nprob) return;
     const int l = threadIdx.x & 63;
     const Prob P = prob(a, p);
 
-    if (which == 0) {  // d_init_var_mpc_soft_tv (d_aux_ip_soft_lib4.c:38-165), ng = 0
+    if (which == SOFT_INIT) {  // d_init_var_mpc_soft_tv (d_aux_ip_soft_lib4.c:38-165), ng = 0
         if (!a.warm_start)
             for (int q = 0; q < a.nq; q++) {
                 const Lane L = lane_at(a, q);
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64) void hk_soft_pass(SoftArgs a, int which) {
     const int kk = P.ist[0];
     double* stat = P.stat + 5 * kk;
 
-    if (which == 1) {  // d_update_hessian_mpc_soft_tv (:167-506), sigma mu = 0
+    if (which == SOFT_HESS) {  // d_update_hessian_mpc_soft_tv (:167-506), sigma mu = 0
         for (int q = 0; q < a.nq; q++) {
             const Lane L = lane_at(a, q);
             if (!L.ok) continue;
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(64) void hk_soft_pass(SoftArgs a, int which) {
         return;
     }
 
-    if (which == 2) {  // predictor: alpha, mu_aff, sigma, then the corrector gradient
+    if (which == SOFT_PRED) {  // predictor: alpha, mu_aff, sigma, then the corrector gradient
         double alpha = soft_alpha(a, P);
         if (l == 0) {
             stat[0] = P.scal[2];
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(64) void hk_soft_pass(SoftArgs a, int which) {
         return;
     }
 
-    // which == 3: corrector alpha, d_update_var_mpc_soft_tv (:806-924), exit test (d_ip2_soft.c:333-535)
+    // which == SOFT_CORR: corrector alpha, d_update_var_mpc_soft_tv (:806-924), exit test (d_ip2_soft.c:333-535)
     double alpha = soft_alpha(a, P);
     if (l == 0) {
         stat[0] = P.scal[2];

@@ -11,6 +11,9 @@
 // lands in the reference.  Plain C layout; every pointer is a device pointer; offsets in doubles.
 #pragma once
 
+// The passes of hk_soft_pass (the `which` of hk_soft_launch), in the order of one iteration after SOFT_INIT.
+enum HkSoftPass { SOFT_INIT = 0, SOFT_HESS = 1, SOFT_PRED = 2, SOFT_CORR = 3 };
+
 struct SoftStage {
     int nu, nx, nx1;      // sizes (nx1 = nx_{k+1}, 0 at k = N)
     int nb, ns, pnb, pns;  // hard / soft boxes and their padded counts

@@ -11,6 +11,7 @@
 // one barrier per dependency step (one per Cholesky column).
 #include <hip/hip_runtime.h>
 
+#include "hk_launch.h"
 #include "hk_wide_core.h"
 
 #ifdef HK_STAMPS
@@ -876,12 +877,12 @@ extern "C" int hk_wide_launch(int which, const void* args, int count, int lds_do
     if (count <= 0) return 0;
     const size_t lds = (size_t)lds_doubles * sizeof(double);
     switch (which) {
-        case 0: {
+        case WL_SV: {
             const WideArgs& a = *static_cast<const WideArgs*>(args);
             hipLaunchKernelGGL(hk_wide_sv, dim3(count), dim3(WT), lds, stream, a);
             break;
         }
-        case 1: {
+        case WL_PCOND: {
             const PcArgs& a = *static_cast<const PcArgs*>(args);
             if (a.gm <= 4)
                 hipLaunchKernelGGL(hk_pcond<4>, dim3(a.N2, count), dim3(WT), lds, stream, a);
@@ -889,12 +890,12 @@ extern "C" int hk_wide_launch(int which, const void* args, int count, int lds_do
                 hipLaunchKernelGGL(hk_pcond<8>, dim3(a.N2, count), dim3(WT), lds, stream, a);
             break;
         }
-        case 2: {
+        case WL_PEXPAND: {
             const PxArgs& a = *static_cast<const PxArgs*>(args);
             hipLaunchKernelGGL(hk_pexpand, dim3(a.N2, count), dim3(WT), lds, stream, a);
             break;
         }
-        case 3: {
+        case WL_TRS: {
             const WideArgs& a = *static_cast<const WideArgs*>(args);
             hipLaunchKernelGGL(hk_wide_trs, dim3(count), dim3(WT), lds, stream, a);
             break;

@@ -6,6 +6,14 @@
 // staged through LDS as dense column-major tiles.  Plain C layout; every pointer is a device pointer.
 #pragma once
 
+// Launch ids of hk_wide_launch (hk_wide.hip) and the argument block each takes.
+enum HkWideLaunch {
+    WL_SV = 0,       // hk_wide_sv, WideArgs
+    WL_PCOND = 1,    // hk_pcond, PcArgs
+    WL_PEXPAND = 2,  // hk_pexpand, PxArgs
+    WL_TRS = 3,      // hk_wide_trs, WideArgs
+};
+
 // One stage of a wide problem (ints; offsets in doubles inside one problem's arrays).
 struct WideStage {
     int nu, nx, nx1, nu1;  // sizes of stage k and k+1 (nx1 = nu1 = 0 at k = N)

@@ -1,37 +1,19 @@
 // hk_wide_host.h -- host-side helpers of the wide-stage path shared by hpmpc_capi_wide.cpp (Riccati, condensing)
-// and hpmpc_capi_wide_ipm.cpp (the IPM on wide stages): the packed per-problem layout of a wide problem, a
-// thread-local device context for the host-buffer entry points, and the launch wrapper.
+// and hpmpc_capi_wide_ipm.cpp (the IPM on wide stages): the packed per-problem layout of a wide problem, the byte
+// carve of the staging arena (the thread's device context, g_dev of hk_host.h) and the launch wrapper.
 #pragma once
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
-#include "hpmpc_api.h"
+#include "hk_host.h"
 #include "hk_wide_args.h"
-
-extern "C" int hk_wide_launch(int which, const void* args, int count, int lds_doubles, hipStream_t stream);
-extern "C" void hk_set_error(int code, const char* what);
 
 namespace {
 
-constexpr int BS = 4, NCL = 2;
 constexpr int LDS_MAX_DOUBLES = 65536 / 8;
 
-inline int rup(int n, int m) { return (n + m - 1) / m * m; }
-inline double& P4(double* A, int sd, int i, int j) { return A[(i / BS) * BS * sd + i % BS + BS * j]; }
 inline int poff(int j, int nz) { return j * nz - (j * (j - 1)) / 2; }
-
-bool hip_ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    char msg[256];
-    snprintf(msg, sizeof msg, "HIP error in %s: %s", what, hipGetErrorString(e));
-    hk_set_error(HPMPC_MI355X_EHIP, msg);
-    return false;
-}
 
 // One problem's packed layout on the wide path (offsets in doubles; idxb in ints).
 struct WLayout {
@@ -98,42 +80,6 @@ WLayout make_layout(int N, const int* nx, const int* nu, const int* nb, const in
     if (L.nG == 0) L.nG = 1;
     return L;
 }
-
-// Thread-local device context of the host-buffer entry points: one stream, a growable device arena and
-// its pinned staging twin.
-struct WCtx {
-    hipStream_t stream = nullptr;
-    char* dev = nullptr;
-    char* host = nullptr;
-    size_t cap = 0;
-    ~WCtx() {
-        if (dev) (void)hipFree(dev);
-        if (host) (void)hipHostFree(host);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    bool ensure(size_t bytes) {
-        if (!stream && !hip_ok(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "stream create")) return false;
-        if (bytes > cap) {
-            if (dev) (void)hipFree(dev);
-            if (host) (void)hipHostFree(host);
-            dev = host = nullptr;
-            cap = 0;
-            if (!hip_ok(hipMalloc((void**)&dev, bytes), "wide device arena")) return false;
-            if (!hip_ok(hipHostMalloc((void**)&host, bytes, 0), "wide pinned arena")) return false;
-            cap = bytes;
-        }
-        memset(host, 0, bytes);
-        return true;
-    }
-    bool up(size_t bytes) {
-        return hip_ok(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream), "H2D");
-    }
-    bool down(size_t bytes) {
-        return hip_ok(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream), "D2H") &&
-               hip_ok(hipStreamSynchronize(stream), "sync");
-    }
-};
-thread_local WCtx g_w;
 
 // Byte carve of the staging arena.
 struct Carve {

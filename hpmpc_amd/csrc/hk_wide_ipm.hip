@@ -17,6 +17,7 @@
 // restatement is oracle/hpmpc_oracle.c ipm_core); each pass below names the reference routine it restates.
 #include <hip/hip_runtime.h>
 
+#include "hk_launch.h"
 #include "hk_launch_guard.h"
 
 #ifdef HK_STAMPS

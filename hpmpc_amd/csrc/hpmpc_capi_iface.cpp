@@ -18,15 +18,9 @@
 #include <cstring>
 #include <vector>
 
-#include "hpmpc_api.h"
-
-extern "C" void hk_set_error(int code, const char* what);
+#include "hk_host.h"
 
 namespace {
-
-constexpr int BS = 4, NCL = 2;
-inline int rup(int n, int m) { return (n + m - 1) / m * m; }
-inline double& P4(double* A, int sd, int i, int j) { return A[(i / BS) * BS * sd + i % BS + BS * j]; }
 
 // Dense m x n block (element (i, j) at A[i + j*lda]) into a lib4 matrix at row offset r0; tran: its transpose.
 void pack(const double* A, int m, int n, int lda, bool tran, double* pA, int sd, int r0) {

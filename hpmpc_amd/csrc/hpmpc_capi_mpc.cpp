@@ -37,14 +37,10 @@
 #include <cstring>
 #include <vector>
 
-#include "hpmpc_api.h"
-
-extern "C" void hk_set_error(int code, const char* what);
+#include "hk_host.h"
 
 namespace {
 
-constexpr int BS = 4, NCL = 2;
-inline int rup(int n, int m) { return (n + m - 1) / m * m; }
 inline long li(int sd, int i, int j) { return (long)(i / BS) * BS * sd + i % BS + BS * j; }
 
 struct Mpc {

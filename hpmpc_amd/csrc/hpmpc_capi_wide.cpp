@@ -1,5 +1,5 @@
 // hpmpc_capi_wide.cpp -- host side of the wide-stage path (hk_wide.hip):
-//   * d_back_ric_rec_sv_tv_res for stages beyond the 16-wide register tile (routed here by hpmpc_capi.cpp);
+//   * d_back_ric_rec_sv_tv_res for stages beyond the 16-wide register tile (routed here by hpmpc_capi_dropin.cpp);
 //   * partial condensing, the §8f #1 row: d_part_cond_compute_problem_size / _work_space_size_bytes /
 //     _memory_space_size_bytes / d_part_cond / d_part_expand_work_space_size_bytes / d_part_expand_solution
 //     (lqcp_solvers/d_part_cond.c:694-1308) with the reference prototypes, on host lib4 buffers;
@@ -9,7 +9,7 @@
 
 
 // ------------------------------------------------------------------------------------------------
-// d_back_ric_rec_sv_tv_res on wide stages (called by hpmpc_capi.cpp when the tile path does not fit).
+// d_back_ric_rec_sv_tv_res on wide stages (called by hpmpc_capi_dropin.cpp when the tile path does not fit).
 // ------------------------------------------------------------------------------------------------
 extern "C" long long hk_wide_factor_bytes(int N, const int* nx, const int* nu) {
     long long s = 0;
@@ -76,8 +76,8 @@ extern "C" void hk_wide_sv_entry(int N, int* nx, int* nu, int* nb, int** idxb, i
     const size_t oSt = c.take(sizeof(WideStage) * (N + 1)), oB = c.take(8 * L.nB), oR = c.take(8 * L.nR),
                  oF = c.take(8 * L.nL), oU = c.take(8 * L.nU), oP = c.take(8 * L.nP), oPb = c.take(8 * L.nP);
     const GenStage gs = carve_general(L, c);
-    if (!g_w.ensure(c.o)) return;
-    char* H = g_w.host;
+    if (!g_dev.ensure(c.o)) return;
+    char* H = g_dev.host;
     memcpy(H + oSt, L.st.data(), sizeof(WideStage) * (N + 1));
     double* HB = reinterpret_cast<double*>(H + oB);
     double* HR = reinterpret_cast<double*>(H + oR);
@@ -100,7 +100,7 @@ extern "C" void hk_wide_sv_entry(int N, int* nx, int* nu, int* nb, int** idxb, i
         }
     }
     stage_general(L, gs, H, hpDCt, Qx, qx);
-    char* D = g_w.dev;
+    char* D = g_dev.dev;
     WideArgs a;
     memset(&a, 0, sizeof a);
     general_args(L, gs, D, a);
@@ -121,7 +121,7 @@ extern "C" void hk_wide_sv_entry(int N, int* nx, int* nu, int* nb, int** idxb, i
     a.offST = L.offST;
     a.ldW = L.ldW;
     a.ldX = L.ldX;
-    if (!g_w.up(c.o) || !launch(0, &a, 1, L.lds, g_w.stream, "hk_wide_sv") || !g_w.down(c.o)) return;
+    if (!g_dev.up(c.o) || !launch(WL_SV, &a, 1, L.lds, g_dev.stream, "hk_wide_sv") || !g_dev.down(c.o)) return;
     const double* HU = reinterpret_cast<const double*>(H + oU);
     const double* HP = reinterpret_cast<const double*>(H + oP);
     const double* HPb = reinterpret_cast<const double*>(H + oPb);
@@ -159,8 +159,8 @@ extern "C" void hk_wide_trf_entry(int N, int* nx, int* nu, int* nb, int** idxb, 
     const size_t oSt = c.take(sizeof(WideStage) * (N + 1)), oB = c.take(8 * L.nB), oR = c.take(8 * L.nR),
                  oF = c.take(8 * L.nL), oU = c.take(8 * L.nU), oP = c.take(8 * L.nP);
     const GenStage gs = carve_general(L, c);
-    if (!g_w.ensure(c.o)) return;
-    char* H = g_w.host;
+    if (!g_dev.ensure(c.o)) return;
+    char* H = g_dev.host;
     memcpy(H + oSt, L.st.data(), sizeof(WideStage) * (N + 1));
     double* HB = reinterpret_cast<double*>(H + oB);
     double* HR = reinterpret_cast<double*>(H + oR);
@@ -175,7 +175,7 @@ extern "C" void hk_wide_trf_entry(int N, int* nx, int* nu, int* nb, int** idxb, 
         if (k < N) memcpy(HB + s.oB, hpBAbt[k], (size_t)rup(nux + 1, BS) * s.sdB * sizeof(double));
     }
     stage_general(L, gs, H, hpDCt, Qx, nullptr);
-    char* D = g_w.dev;
+    char* D = g_dev.dev;
     WideArgs a;
     wide_args(L, a);
     general_args(L, gs, D, a);
@@ -186,7 +186,7 @@ extern "C" void hk_wide_trf_entry(int N, int* nx, int* nu, int* nb, int** idxb, 
     a.ws = reinterpret_cast<double*>(D + oF);
     a.ux = reinterpret_cast<double*>(D + oU);
     a.pi = a.Pb = reinterpret_cast<double*>(D + oP);
-    if (!g_w.up(c.o) || !launch(0, &a, 1, L.lds, g_w.stream, "hk_wide_sv(trf)") || !g_w.down(c.o)) return;
+    if (!g_dev.up(c.o) || !launch(WL_SV, &a, 1, L.lds, g_dev.stream, "hk_wide_sv(trf)") || !g_dev.down(c.o)) return;
     memcpy(memory, H + oF, 8 * L.nL);
 }
 
@@ -201,8 +201,8 @@ extern "C" void hk_wide_trs_entry(int N, int* nx, int* nu, int* nb, int** idxb, 
     const size_t oSt = c.take(sizeof(WideStage) * (N + 1)), oB = c.take(8 * L.nB), oF = c.take(8 * L.nL),
                  oU = c.take(8 * L.nU), oP = c.take(8 * L.nP), oPb = c.take(8 * L.nP), ob = c.take(8 * L.nP),
                  oq = c.take(8 * L.nU), oqx = c.take(8 * L.nD), oI = c.take(4 * L.nI), oG = c.take(8 * L.nG);
-    if (!g_w.ensure(c.o)) return;
-    char* H = g_w.host;
+    if (!g_dev.ensure(c.o)) return;
+    char* H = g_dev.host;
     memcpy(H + oSt, L.st.data(), sizeof(WideStage) * (N + 1));
     memcpy(H + oF, memory, 8 * L.nL);
     double* HB = reinterpret_cast<double*>(H + oB);
@@ -230,7 +230,7 @@ extern "C" void hk_wide_trs_entry(int N, int* nx, int* nu, int* nb, int** idxb, 
             if (!compute_Pb) memcpy(HPb + s.oP, hPb[k], s.nx1 * sizeof(double));
         }
     }
-    char* D = g_w.dev;
+    char* D = g_dev.dev;
     WideArgs a;
     wide_args(L, a);
     a.st = reinterpret_cast<const WideStage*>(D + oSt);
@@ -246,7 +246,7 @@ extern "C" void hk_wide_trs_entry(int N, int* nx, int* nu, int* nb, int** idxb, 
     if (L.any_ng) a.DCt = reinterpret_cast<const double*>(D + oG);
     a.compute_pi = compute_pi;
     a.compute_Pb = compute_Pb;
-    if (!g_w.up(c.o) || !launch(3, &a, 1, L.lds, g_w.stream, "hk_wide_trs") || !g_w.down(c.o)) return;
+    if (!g_dev.up(c.o) || !launch(WL_TRS, &a, 1, L.lds, g_dev.stream, "hk_wide_trs") || !g_dev.down(c.o)) return;
     const double* HU = reinterpret_cast<const double*>(H + oU);
     const double* HP = reinterpret_cast<const double*>(H + oP);
     for (int k = 0; k <= N; k++) {
@@ -590,8 +590,8 @@ extern "C" void d_part_cond(int N, int* nx, int* nu, int* nb, int** hidxb, int* 
     const size_t oSt = c.take(sizeof(WideStage) * (N + 1)), oBlk = c.take(sizeof(PcBlock) * N2),
                  oIdx = c.take(4 * O.nI), oB = c.take(8 * O.nB), oR = c.take(8 * O.nR), oD = c.take(8 * O.nD),
                  oG = c.take(8 * P.nG), oMem = c.take(8 * mem_doubles);
-    if (!g_w.ensure(c.o)) return;
-    char* H = g_w.host;
+    if (!g_dev.ensure(c.o)) return;
+    char* H = g_dev.host;
     memcpy(H + oSt, O.st.data(), sizeof(WideStage) * (N + 1));
     // condensed outputs go straight into the reference carve inside one buffer (oMem): BAbt2 | RSQrq2 |
     // DCt2 | d2 | idxb2, so the block offsets are absolute within that buffer
@@ -635,7 +635,7 @@ extern "C" void d_part_cond(int N, int* nx, int* nu, int* nb, int** hidxb, int* 
         memcpy(HR + s.oR, hpRSQrq[k], (size_t)rup(nux + 1, BS) * s.sdR * sizeof(double));
         if (nb[k] + ng[k] > 0) memcpy(HD + s.oD, hd[k], (size_t)(2 * s.pnb + 2 * rup(ng[k], BS)) * sizeof(double));
     }
-    char* D = g_w.dev;
+    char* D = g_dev.dev;
     PcArgs a;
     fill_pc_args(P, a);
     a.nprob = 1;
@@ -651,7 +651,7 @@ extern "C" void d_part_cond(int N, int* nx, int* nu, int* nb, int** hidxb, int* 
     a.idxb2 = reinterpret_cast<int*>(mem + P.ref_d);
     a.oR2N = (int)term_off;
     a.nDN = 0;  // the reference aliases hd2[N2] = hd[N] (d_part_cond.c), nothing to copy into the carve
-    if (!g_w.up(c.o) || !launch(1, &a, 1, P.pc_lds, g_w.stream, "hk_pcond") || !g_w.down(c.o)) return;
+    if (!g_dev.up(c.o) || !launch(WL_PCOND, &a, 1, P.pc_lds, g_dev.stream, "hk_pcond") || !g_dev.down(c.o)) return;
     for (int ii = 0; ii <= N2; ii++) {
         nx2[ii] = P.nx2[ii];
         nu2[ii] = P.nu2[ii];
@@ -731,8 +731,8 @@ void cond_part(int ph, int N, const int* nx, const int* nu, const int* nb, int* 
                  oB = c.take(8 * O.nB), oR = c.take(8 * O.nR), oD = c.take(8 * O.nD + 8), oG = c.take(8 * P.nG),
                  oB2 = c.take(8 * nB2), oR2 = c.take(8 * nR2), oG2 = c.take(8 * nG2 + 8), oD2 = c.take(8 * nD2 + 8),
                  oI2 = c.take(4 * nbb + 4);
-    if (!g_w.ensure(c.o)) return;
-    char* H = g_w.host;
+    if (!g_dev.ensure(c.o)) return;
+    char* H = g_dev.host;
     memset(H, 0, c.o);
     memcpy(H + oSt, O.st.data(), sizeof(WideStage) * (N + 1));
     PcBlock blk = b0;
@@ -761,7 +761,7 @@ void cond_part(int ph, int N, const int* nx, const int* nu, const int* nb, int* 
         if (nG2) memcpy(H + oG2, pDCt2, 8 * nG2);
         if (nD2) memcpy(H + oD2, d2, 8 * nD2);
     }
-    char* D = g_w.dev;
+    char* D = g_dev.dev;
     PcArgs a;
     fill_pc_args(P, a);
     a.ph = ph | PC_PART;
@@ -778,7 +778,7 @@ void cond_part(int ph, int N, const int* nx, const int* nu, const int* nb, int* 
     a.DCt2 = reinterpret_cast<double*>(D + oG2);
     a.d2 = reinterpret_cast<double*>(D + oD2);
     a.idxb2 = reinterpret_cast<int*>(D + oI2);
-    if (!g_w.up(c.o) || !launch(1, &a, 1, P.pc_lds, g_w.stream, "hk_pcond") || !g_w.down(c.o)) return;
+    if (!g_dev.up(c.o) || !launch(WL_PCOND, &a, 1, P.pc_lds, g_dev.stream, "hk_pcond") || !g_dev.down(c.o)) return;
     if (ph == PC_BABT) {  // d_part_cond.c:262-303: Gamma_j (r_j x nx_{j+1}) and BAbt2 = Gamma_{N-1}
         const double* B2 = reinterpret_cast<const double*>(H + oB2);
         for (int j = 0; j < N; j++) {
@@ -841,8 +841,8 @@ extern "C" void d_part_expand_solution(int N, int* nx, int* nu, int* nb, int** h
                  oR = c.take(8 * O.nR), ohb = c.take(8 * O.nP), orq = c.take(8 * O.nU), oU2 = c.take(8 * C.nU),
                  oP2 = c.take(8 * C.nP), oL2 = c.take(8 * C.nD), oT2 = c.take(8 * C.nD), oU = c.take(8 * O.nU),
                  oP = c.take(8 * O.nP), oL = c.take(8 * O.nD), oT = c.take(8 * O.nD);
-    if (!g_w.ensure(c.o)) return;
-    char* H = g_w.host;
+    if (!g_dev.ensure(c.o)) return;
+    char* H = g_dev.host;
     memcpy(H + oSt, O.st.data(), sizeof(WideStage) * (N + 1));
     memcpy(H + oSt2, C.st.data(), sizeof(WideStage) * (N2 + 1));
     memcpy(H + oBlk, P.blk.data(), sizeof(PcBlock) * N2);
@@ -868,7 +868,7 @@ extern "C" void d_part_expand_solution(int N, int* nx, int* nu, int* nb, int** h
             memcpy(dp(oT2) + s.oD, ht2[k], nc * sizeof(double));
         }
     }
-    char* D = g_w.dev;
+    char* D = g_dev.dev;
     auto dd = [&](size_t off) { return reinterpret_cast<double*>(D + off); };
     PxArgs a;
     fill_px_args(P, a);
@@ -889,7 +889,7 @@ extern "C" void d_part_expand_solution(int N, int* nx, int* nu, int* nb, int** h
     a.pi = dd(oP);
     a.lam = dd(oL);
     a.t = dd(oT);
-    if (!g_w.up(c.o) || !launch(2, &a, 1, P.px_lds, g_w.stream, "hk_pexpand") || !g_w.down(c.o)) return;
+    if (!g_dev.up(c.o) || !launch(WL_PEXPAND, &a, 1, P.px_lds, g_dev.stream, "hk_pexpand") || !g_dev.down(c.o)) return;
     for (int k = 0; k <= N; k++) {
         const WideStage& s = O.st[k];
         memcpy(hux[k], dp(oU) + s.oU, (s.nu + s.nx) * sizeof(double));
@@ -915,10 +915,6 @@ extern "C" void d_part_expand_solution(int N, int* nx, int* nu, int* nb, int** h
 // ------------------------------------------------------------------------------------------------
 // Batched device API of the partial-condensing pipeline (data resident in HBM, problem-major).
 // ------------------------------------------------------------------------------------------------
-extern "C" hpmpc_mi355x_wide_plan* hpmpc_mi355x_wide_plan_create(int N, const int* nx, const int* nu, const int* nb,
-                                                                 const int* const* idxb, const int* ng);
-extern "C" void hpmpc_mi355x_wide_plan_destroy(hpmpc_mi355x_wide_plan* q);
-
 struct hpmpc_mi355x_pcond_plan {
     PcPlan P;
     hpmpc_mi355x_wide_plan* wide = nullptr;  // the condensed problem's IPM plan (null: beyond the wide IPM)
@@ -1057,7 +1053,7 @@ extern "C" int hpmpc_mi355x_pcond_batch(const hpmpc_mi355x_pcond_plan* q, int np
     a.d2 = d2;
     a.idxb2 = q->d_idxb2;
     if (const char* e = getenv("HK_PCOND_SKIP")) a.skip = atoi(e);  // profiling only
-    return launch(1, &a, count, q->P.pc_lds, (hipStream_t)stream, "hk_pcond") ? 0 : HPMPC_MI355X_EHIP;
+    return launch(WL_PCOND, &a, count, q->P.pc_lds, (hipStream_t)stream, "hk_pcond") ? 0 : HPMPC_MI355X_EHIP;
 }
 
 extern "C" int hpmpc_mi355x_pcond_ric_sv_batch(const hpmpc_mi355x_pcond_plan* q, int nprob, int p0, int count,
@@ -1095,7 +1091,7 @@ extern "C" int hpmpc_mi355x_pcond_ric_sv_batch(const hpmpc_mi355x_pcond_plan* q,
     a.ldW = C.ldW;
     a.ldX = C.ldX;
     if (const char* e = getenv("HK_WIDE_SKIP")) a.skip = atoi(e);  // profiling only
-    return launch(0, &a, count, C.lds, (hipStream_t)stream, "hk_wide_sv") ? 0 : HPMPC_MI355X_EHIP;
+    return launch(WL_SV, &a, count, C.lds, (hipStream_t)stream, "hk_wide_sv") ? 0 : HPMPC_MI355X_EHIP;
 }
 
 extern "C" int hpmpc_mi355x_pexpand_batch(const hpmpc_mi355x_pcond_plan* q, int nprob, int p0, int count,
@@ -1122,5 +1118,5 @@ extern "C" int hpmpc_mi355x_pexpand_batch(const hpmpc_mi355x_pcond_plan* q, int 
     a.pi = pi;
     a.lam = lam;
     a.t = t;
-    return launch(2, &a, count, q->P.px_lds, (hipStream_t)stream, "hk_pexpand") ? 0 : HPMPC_MI355X_EHIP;
+    return launch(WL_PEXPAND, &a, count, q->P.px_lds, (hipStream_t)stream, "hk_pexpand") ? 0 : HPMPC_MI355X_EHIP;
 }

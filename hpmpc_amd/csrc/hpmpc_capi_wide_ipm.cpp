@@ -1,6 +1,6 @@
 // hpmpc_capi_wide_ipm.cpp -- host side of the IPM on wide stages (hk_wide_ipm.hip).
 //
-// hpmpc_capi.cpp routes the reference-named IPM entry points here when a problem does not fit the 16-wide
+// hpmpc_capi_dropin.cpp routes the reference-named IPM entry points here when a problem does not fit the 16-wide
 // register tile (nu+nx > 16, round_up(nu,4)+nx > 16, or more than 16 box + general slots in a stage):
 //   d_ip2_res_mpc_hard_tv, d_ip2_res_mpc_hard_tv_single_newton_step, d_kkt_solve_new_rhs_res_mpc_hard_tv,
 //   d_res_res_mpc_hard_tv (mpc_solvers/d_ip2_res_hard.c, c99/d_res_ip_res_hard.c), and d_ip2_mpc_hard_tv,
@@ -11,7 +11,6 @@
 // KKT re-solves find what the IPM left; its size is d_ip2_res_mpc_hard_tv_work_space_size_bytes.
 #include "hk_wide_host.h"
 
-extern "C" int hk_wide_ipm_launch(const WideIpmArgs* a, int count, int lds_doubles, hipStream_t stream);
 namespace {
 // the wide IPM's LDS: the Riccati carve, 8 doubles of reduction scratch, the DCt chunk-limit table ((N+1) x 8 ints
 // and a flag, hk_wide_core.h)
@@ -238,20 +237,20 @@ void fill_args(const WIpm& W, const Stage& S, char* D, int N, WideIpmArgs& a) {
 }
 
 bool run(const WIpm& W, const Stage& S, const WideIpmArgs& a) {
-    if (!g_w.up(S.total)) return false;
-    const int e = hk_wide_ipm_launch(&a, 1, ipm_lds(W.L), g_w.stream);
+    if (!g_dev.up(S.total)) return false;
+    const int e = hk_wide_ipm_launch(&a, 1, ipm_lds(W.L), g_dev.stream);
     if (e) {
         char msg[96];
         snprintf(msg, sizeof msg, "hk_wide_ipm launch %s (%d)", e == -2 ? "refused: scratch / LDS beyond the limits" : "failed", e);
         hk_set_error(e == -2 ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP, msg);
         return false;
     }
-    return g_w.down(S.total);
+    return g_dev.down(S.total);
 }
 
 }  // namespace
 
-// bytes of the wide IPM's work image for these sizes (hpmpc_capi.cpp reports the larger of this and the tile
+// bytes of the wide IPM's work image for these sizes (hpmpc_capi_dropin.cpp reports the larger of this and the tile
 // path's image as d_ip2_res_mpc_hard_tv_work_space_size_bytes)
 extern "C" long long hk_wide_ipm_bytes(int N, const int* nx, const int* nu, const int* nb, const int* ng) {
     return make_ipm(N, nx, nu, nb, ng).nIW * 8;
@@ -278,8 +277,8 @@ extern "C" int hk_wide_ipm_entry(int mode, int* kk, int k_max, double mu0, doubl
     }
     fill_slots(W, N, idxb);
     const Stage S = carve(W, N, k_max);
-    if (!g_w.ensure(S.total)) return HPMPC_MI355X_EHIP;
-    char* H = g_w.host;
+    if (!g_dev.ensure(S.total)) return HPMPC_MI355X_EHIP;
+    char* H = g_dev.host;
     stage_common(W, S, H, N, idxb, pBAbt, pQ, pDCt);
     cvec_in(W, S, S.oD, H, N, d);
     double* HU = reinterpret_cast<double*>(H + S.oU);
@@ -302,7 +301,7 @@ extern "C" int hk_wide_ipm_entry(int mode, int* kk, int k_max, double mu0, doubl
         uvec_in(W, HU, N, ux);
     }
     WideIpmArgs a;
-    fill_args(W, S, g_w.dev, N, a);
+    fill_args(W, S, g_dev.dev, N, a);
     a.mode = mode;
     a.k_max = k_max;
     a.warm_start = warm_start;
@@ -341,19 +340,19 @@ extern "C" void hk_wide_kkt_entry(int p1, int N, int* nx, int* nu_N, int* nb, in
     if (!ipm_check(W, N, nx, nu.data(), nb, idxb, ng)) return;
     fill_slots(W, N, idxb);
     const Stage S = carve(W, N, 1);
-    if (!g_w.ensure(S.total)) return;
-    char* H = g_w.host;
+    if (!g_dev.ensure(S.total)) return;
+    char* H = g_dev.host;
     stage_common(W, S, H, N, idxb, pBAbt, pQ, pDCt);
     cvec_in(W, S, S.oD, H, N, d);
     uvec_in(W, reinterpret_cast<double*>(H + S.ovq), N, q);
     pvec_in(W, reinterpret_cast<double*>(H + S.ovb), N, b);
     memcpy(H + S.oIW, work, W.nIW * sizeof(double));
     WideIpmArgs a;
-    fill_args(W, S, g_w.dev, N, a);
+    fill_args(W, S, g_dev.dev, N, a);
     a.mode = p1 ? WI_KKT_P1 : WI_KKT_RES;
     a.compute_mult = compute_mult;
-    a.vb = reinterpret_cast<const double*>(g_w.dev + S.ovb);
-    a.vq = reinterpret_cast<const double*>(g_w.dev + S.ovq);
+    a.vb = reinterpret_cast<const double*>(g_dev.dev + S.ovb);
+    a.vq = reinterpret_cast<const double*>(g_dev.dev + S.ovq);
     if (!run(W, S, a)) return;
     const double* HU = reinterpret_cast<const double*>(H + S.oU);
     const double* HP = reinterpret_cast<const double*>(H + S.oP);
@@ -376,8 +375,8 @@ extern "C" void hk_wide_res_entry(int plain, int N, int* nx, int* nu, int* nb, i
     if (!ipm_check(W, N, nx, nu, nb, idxb, ng)) return;
     fill_slots(W, N, idxb);
     const Stage S = carve(W, N, 1);
-    if (!g_w.ensure(S.total)) return;
-    char* H = g_w.host;
+    if (!g_dev.ensure(S.total)) return;
+    char* H = g_dev.host;
     stage_common(W, S, H, N, idxb, hpBAbt, hpQ, hpDCt);
     cvec_in(W, S, S.oD, H, N, hd);
     cvec_in(W, S, S.oLam, H, N, hlam);
@@ -388,10 +387,10 @@ extern "C" void hk_wide_res_entry(int plain, int N, int* nx, int* nu, int* nb, i
     pvec_in(W, reinterpret_cast<double*>(H + S.ovb), N, hb);
     reinterpret_cast<double*>(H + S.oCtl + 8)[0] = *mu;  // unchanged without constraints (d_res_ip_res_hard.c:309-313)
     WideIpmArgs a;
-    fill_args(W, S, g_w.dev, N, a);
+    fill_args(W, S, g_dev.dev, N, a);
     a.mode = plain ? WI_RES_PLAIN : WI_RES;
-    a.vb = reinterpret_cast<const double*>(g_w.dev + S.ovb);
-    a.vq = reinterpret_cast<const double*>(g_w.dev + S.ovq);
+    a.vb = reinterpret_cast<const double*>(g_dev.dev + S.ovb);
+    a.vq = reinterpret_cast<const double*>(g_dev.dev + S.ovq);
     if (!run(W, S, a)) return;
     const double* IW = reinterpret_cast<const double*>(H + S.oIW);
     for (int k = 0; k <= N; k++) {

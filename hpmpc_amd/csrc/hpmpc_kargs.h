@@ -3,6 +3,35 @@
 // stride given next to them (0 = shared by all problems, i.e. time-invariant / aliased data).
 #pragma once
 
+// Per-stage strides of the tile path's arrays, for the kernels and for the host carves.
+constexpr int FSTRIDE = 352;  // factor doubles per stage: 4 regs x 64 lanes + l (16) + inv_diag (16) + KG (64)
+constexpr int V16 = 16;       // per-stage stride of tile/state vectors
+constexpr int V32 = 32;       // per-stage stride of constraint vectors ([lb | pad | ub | pad])
+
+// Launch ids of hk_launch (hpmpc_kernels.hip launch_t), and K_SV of the ric2 variant's hk_launch_ric2.
+enum HkLaunch {
+    K_SV = 0,      // hk_ric_sv
+    K_TRF = 1,     // hk_ric_trf
+    K_TRS = 2,     // hk_ric_trs
+    K_RES = 3,     // hk_res
+    K_IPM = 4,     // the batched solve: K_PASS_INIT, then k_max x (FACT, PRED, CORR, UPDATE)
+    K_KKT = 5,     // hk_kkt_new_rhs
+    K_KKT_P1 = 6,  // hk_kkt_new_rhs_p1
+    // single IPM pass kernels; hpmpc_mi355x_ipm_pass and the profiled solve compute these as K_PASS_INIT + pass
+    K_PASS_INIT = 10,
+    K_PASS_FACT = 11,
+    K_PASS_PRED = 12,
+    K_PASS_CORR = 13,
+    K_PASS_UPDATE = 14,
+    K_SOLO = 15,           // the whole IPM of a problem in one launch (hk_ipm_solo_mw, or hk_ipm_solo)
+    K_SOLO_1W = 16,        // the same, always the single-wave kernel
+    K_QDRAIN = 17,         // the queue's drain (hk_ipm_qdrain_mw)
+    K_PASS_PREDCORR = 18,  // the queue's tick: FACT, PREDCORR (predictor + corrector), UPDATE
+};
+static_assert(K_PASS_FACT == K_PASS_INIT + 1 && K_PASS_PRED == K_PASS_INIT + 2 && K_PASS_CORR == K_PASS_INIT + 3 &&
+                  K_PASS_UPDATE == K_PASS_INIT + 4,
+              "the pass ids are consecutive: the host computes them as K_PASS_INIT + pass and K_PASS_FACT + i % 4");
+
 struct KArgs {
     int N, nprob, p0;             // horizon, problems in the batch, first problem of this launch
     int nbt;                      // sum of nb + ng over the stages

@@ -6,6 +6,7 @@
 // All IPM control flow (iteration count, step length, mu) is per wave, so problems that converge
 // early simply retire their wave.
 #include "hk_ipm_body.h"
+#include "hk_launch.h"
 #include "hk_mw.h"
 #include <cstdlib>
 
@@ -658,11 +659,11 @@ static int launch_t(int which, const KArgs* a, int count, hipStream_t stream) {
     dim3 grid(count), block(64);
     const size_t lds = sizeof(Scratch) + (size_t)(a->N + 1) * (sizeof(StageInfo) + 40);
     switch (which) {
-        case 0: hipLaunchKernelGGL(hk_ric_sv<FX>, grid, block, lds, stream, *a); break;
-        case 1: hipLaunchKernelGGL(hk_ric_trf<FX>, grid, block, lds, stream, *a); break;
-        case 2: hipLaunchKernelGGL(hk_ric_trs<FX>, grid, block, lds, stream, *a); break;
-        case 3: hipLaunchKernelGGL(hk_res<FX>, grid, block, lds, stream, *a); break;
-        case 4:
+        case K_SV: hipLaunchKernelGGL(hk_ric_sv<FX>, grid, block, lds, stream, *a); break;
+        case K_TRF: hipLaunchKernelGGL(hk_ric_trf<FX>, grid, block, lds, stream, *a); break;
+        case K_TRS: hipLaunchKernelGGL(hk_ric_trs<FX>, grid, block, lds, stream, *a); break;
+        case K_RES: hipLaunchKernelGGL(hk_res<FX>, grid, block, lds, stream, *a); break;
+        case K_IPM:
             hipLaunchKernelGGL(hk_ipm_init<FX>, grid, block, lds, stream, *a);
             for (int it = 0; it < a->k_max; it++) {
                 hipLaunchKernelGGL(hk_ipm_fact<FX>, grid, block, lds, stream, *a);
@@ -671,26 +672,26 @@ static int launch_t(int which, const KArgs* a, int count, hipStream_t stream) {
                 hipLaunchKernelGGL(hk_ipm_update<FX>, grid, block, lds, stream, *a);
             }
             break;
-        case 5: hipLaunchKernelGGL(hk_kkt_new_rhs<FX>, grid, block, lds, stream, *a); break;
-        case 6: hipLaunchKernelGGL(hk_kkt_new_rhs_p1<FX>, grid, block, lds, stream, *a); break;
-        // single IPM pass kernels (hpmpc_mi355x_ipm_pass): the batched solve is 10, then k_max x (11..14)
-        case 10: hipLaunchKernelGGL(hk_ipm_init<FX>, grid, block, lds, stream, *a); break;
-        case 11: hipLaunchKernelGGL(hk_ipm_fact<FX>, grid, block, lds, stream, *a); break;
-        case 12: hipLaunchKernelGGL(hk_ipm_pred<FX>, grid, block, lds, stream, *a); break;
-        case 13: hipLaunchKernelGGL(hk_ipm_corr<FX>, grid, block, lds, stream, *a); break;
-        case 14: hipLaunchKernelGGL(hk_ipm_update<FX>, grid, block, lds, stream, *a); break;
-        // the queue's tick: fact (11), predictor + corrector (18), update (14)
-        case 18: hipLaunchKernelGGL(hk_ipm_predcorr<FX>, grid, block, lds, stream, *a); break;
+        case K_KKT: hipLaunchKernelGGL(hk_kkt_new_rhs<FX>, grid, block, lds, stream, *a); break;
+        case K_KKT_P1: hipLaunchKernelGGL(hk_kkt_new_rhs_p1<FX>, grid, block, lds, stream, *a); break;
+        // single IPM pass kernels (hpmpc_mi355x_ipm_pass): the batched solve is INIT, then k_max x (FACT .. UPDATE)
+        case K_PASS_INIT: hipLaunchKernelGGL(hk_ipm_init<FX>, grid, block, lds, stream, *a); break;
+        case K_PASS_FACT: hipLaunchKernelGGL(hk_ipm_fact<FX>, grid, block, lds, stream, *a); break;
+        case K_PASS_PRED: hipLaunchKernelGGL(hk_ipm_pred<FX>, grid, block, lds, stream, *a); break;
+        case K_PASS_CORR: hipLaunchKernelGGL(hk_ipm_corr<FX>, grid, block, lds, stream, *a); break;
+        case K_PASS_UPDATE: hipLaunchKernelGGL(hk_ipm_update<FX>, grid, block, lds, stream, *a); break;
+        // the queue's tick: fact, predictor + corrector, update
+        case K_PASS_PREDCORR: hipLaunchKernelGGL(hk_ipm_predcorr<FX>, grid, block, lds, stream, *a); break;
         // the whole IPM per problem in one launch (hk_ipm_solo)
-        case 15:
-        case 16: {
+        case K_SOLO:
+        case K_SOLO_1W: {
             // one problem per 256-thread workgroup (hk_ipm_solo_mw) unless HPMPC_MI355X_SOLO=1 asks for the
-            // single-wave kernel (which == 16 forces it), the horizon exceeds the kernel's LDS tables, or the
+            // single-wave kernel (K_SOLO_1W forces it), the horizon exceeds the kernel's LDS tables, or the
             // launch guard (static + dynamic LDS, private segment vs the stack limit, launch bound; read once, with
             // thread-safe static initialisation) refuses it: then the single-wave kernel runs instead
             static const HkKernelLimits lim_mw(reinterpret_cast<const void*>(&hk_ipm_solo_mw<FX>));
             const char* env = getenv("HPMPC_MI355X_SOLO");
-            const bool single = which == 16 || (env && env[0] == '1');
+            const bool single = which == K_SOLO_1W || (env && env[0] == '1');
             const size_t lds_mw = mw_lds_bytes(a->N);
             hipLaunchKernelGGL(hk_ipm_init<FX>, grid, block, lds, stream, *a);
             if (!single && a->N <= MW_NMAX && lim_mw.check(lds_mw, 256) == 0)
@@ -701,7 +702,7 @@ static int launch_t(int which, const KArgs* a, int count, hipStream_t stream) {
         }
         // the queue's drain (hk_ipm_qdrain_mw): grid = slots, four waves per workgroup; HK_LAUNCH_REFUSED when the
         // horizon or the launch guard rules the multi-wave kernel out (the host then keeps ticking)
-        case 17: {
+        case K_QDRAIN: {
             static const HkKernelLimits lim_dr(reinterpret_cast<const void*>(&hk_ipm_qdrain_mw<FX>));
             const size_t lds_mw = mw_lds_bytes(a->N);
             if (a->N > MW_NMAX || lim_dr.check(lds_mw, 256) != 0) return HK_LAUNCH_REFUSED;

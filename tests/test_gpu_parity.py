@@ -40,6 +40,32 @@ def test_golden_through_c_abi(product, case):
     check_case(case, run_case(product, case))
 
 
+def _same_bits(a, b):
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_same_bits(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return len(a) == len(b) and all(_same_bits(x, y) for x, y in zip(a, b))
+    if a is None or b is None:
+        return a is b
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def test_one_device_context_across_paths(product):
+    """The host-buffer entry points of every host file share one thread-local stream / arena context.  In one thread:
+    a narrow Riccati solve, the wide residual file, the wide IPM file, the soft path, then the first call again.  The
+    arena grows, is re-used by a smaller carve and changes owner between translation units; every call must meet its
+    golden at the golden sweep's tolerance, and the last call's outputs equal the first call's bit for bit."""
+    by = {c.name: c for c in CASES}
+    order = ["sv_tv_N20_nx12_nu4", "resw_N20_nx24_nu6", "ipmw_tv_N15_nx24_nu6", "iface_soft_N12_nx8_nu3",
+             "sv_tv_N20_nx12_nu4"]
+    got = []
+    for name in order:
+        got.append(run_case(product, by[name]))
+        check_case(by[name], got[-1])
+    assert _same_bits(got[0], got[-1])
+
+
 # The reference's inner-stage x-pivot clamp (kernel_dpotrf_c99_lib4.c:555-640): a state whose Hessian diagonal is
 # d <= 1e-15 with cross terms `off` and gradient r.  The P form keeps its cheap record only on stages that pass the
 # clamp certificate (hk_riccati.h cert_ok); these stages fail it and are factorised as the reference does, so the
