@@ -1,12 +1,14 @@
 // hk_plan.h -- the tile path's plan and the one-problem staging carve, shared by the host files of that path:
 // hpmpc_capi.cpp (plan, layout tables, batched API; defines the plan functions below), hpmpc_capi_queue.cpp (the
 // problem queue), hpmpc_capi_dropin.cpp (reference-named hard-constraint entry points; defines the arena functions)
-// and hpmpc_capi_soft.cpp (soft-constraint IPM and residual).
+// hpmpc_capi_soft.cpp (soft-constraint IPM and residual; defines the soft refusals and layout) and
+// hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM).
 #pragma once
 #include <mutex>
 #include <vector>
 
 #include "hk_host.h"
+#include "hk_soft_args.h"
 #include "hpmpc_kargs.h"
 
 struct StageInfoH {  // mirror of hk::StageInfo
@@ -73,3 +75,15 @@ bool run(int which, const KArgs& a, const char* name);  // one-problem launch on
 enum VecKind { VEC_UX, VEC_PI, VEC_CV };
 void vec_in(const hpmpc_mi355x_plan* P, VecKind kind, double* H, size_t off, double** v);
 void vec_out(const hpmpc_mi355x_plan* P, VecKind kind, double** v, const double* H, size_t off);
+
+// hpmpc_capi_soft.cpp: what the soft-constraint IPM refuses and how it lays out its vectors, for the reference-named
+// entry point and the batched one alike.  Both return null, or the reason for HPMPC_MI355X_EUNSUPPORTED.
+struct SoftLayout {
+    std::vector<SoftStage> st;
+    long sC = 0, sD = 0, sZ = 0;  // doubles per problem of t / lam, d, Z / z
+    long sF = 0;                  // the flat Qx / qx | Zl / zl block with the reference's padding
+};
+// ng > 0, nu[N] != 0, N < 1, or a b_k the reference reads outside BAbt_k
+const char* soft_unsupported(int N, const int* nx, const int* nu, const int* ng);
+// the layout; refuses the stray soft-gradient write into a Zl its pass still reads
+const char* soft_layout(int N, const int* nx, const int* nu, const int* nb, const int* ns, SoftLayout& L);

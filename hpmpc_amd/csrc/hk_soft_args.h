@@ -11,7 +11,8 @@
 // lands in the reference.  Plain C layout; every pointer is a device pointer; offsets in doubles.
 #pragma once
 
-// The passes of hk_soft_pass (the `which` of hk_soft_launch), in the order of one iteration after SOFT_INIT.
+// The passes of hk_soft_pass (the `which` of hk_soft_launch), in the order of one iteration after SOFT_INIT
+// (bodies: hk_soft_body.h).
 enum HkSoftPass { SOFT_INIT = 0, SOFT_HESS = 1, SOFT_PRED = 2, SOFT_CORR = 3 };
 
 struct SoftStage {
@@ -26,25 +27,32 @@ struct SoftStage {
     int pad;
 };
 
+// Per-problem arrays are problem-major with the stride next to them; the reference-named entry point runs one
+// problem (nprob = 1), the batched solve (hk_soft_ipm.hip) many, with every work array inside the problem's
+// workspace (stride sW).
 struct SoftArgs {
     int N, nprob, p0, k_max, warm_start, nq;  // nq = ceil((N+1)/4) stage quads
     const SoftStage* st;
     const int* idxb;  // 16 per stage (hard then soft), shared by the batch
     const double *d, *Z, *z;
     long long sD, sZ;
-    double *t, *lam, *dt, *dlam, *lamt, *tinv;
+    double *t, *lam;  // iterate
     long long sC;
-    double* flat;
-    long long sF;
-    double *ux, *pi;    // iterate, V16 per stage
-    double *dux, *dpi;  // Riccati outputs, V16 per stage
-    double *vQx, *vqx;  // Riccati box terms, V16 per stage (slot = position in idxb)
+    double *ux, *pi;  // iterate, V16 per stage
     long long sV;
+    // work arrays, stride sW doubles between problems (ist: 2 sW ints)
+    double *dt, *dlam, *lamt, *tinv;  // like t / lam
+    double* flat;                     // Qx / qx | Zl / zl block
+    double *dux, *dpi;                // Riccati outputs, V16 per stage
+    double *vQx, *vqx;                // Riccati box terms, V16 per stage (slot = position in idxb)
+    double *vb, *vq;                  // Riccati b_k / q_k rows, V16 per stage (filled on the device by the batched init)
+    double* scal;                     // 4: mu, alpha, sigma, mu_aff
+    int* ist;                         // 4: kk, active, ret
+    long long sW;
     double mu0, mu_tol, alpha_min, mu_scal;
-    double* scal;  // per problem, 4: mu, alpha, sigma, mu_aff
-    int* ist;      // per problem, 4: kk, active, ret
     double* stat;  // per problem, 5 k_max
     long long sS;
+    int *kk, *ret;  // per problem (batched solve)
 };
 
 // d_res_mpc_soft_tv (mpc_solvers/d_res_ip_soft.c:38-268): one 256-thread workgroup walks the stages of one

@@ -3,7 +3,6 @@
 #include <algorithm>
 
 #include "hk_plan.h"
-#include "hk_soft_args.h"
 
 // ================================================================================================
 // Soft-constraint IPM d_ip2_mpc_soft_tv (mpc_solvers/d_ip2_soft.c:42-547, include/mpc_solvers.h:69-70):
@@ -12,8 +11,6 @@
 // round_up(nb + ns, 4) <= 16 per stage, b_k read inside BAbt_k with the reference's stride
 // (d_ip2_soft.c:172), and no soft-gradient write of the reference into a Zl its pass still reads.
 // ================================================================================================
-namespace {
-
 const char* soft_unsupported(int N, const int* nx, const int* nu, const int* ng) {
     if (N < 1 || nu[N] != 0) return "soft IPM: N >= 1 and nu[N] = 0 required";
     for (int k = 0; k <= N; k++)
@@ -26,6 +23,55 @@ const char* soft_unsupported(int N, const int* nx, const int* nu, const int* ng)
     }
     return nullptr;
 }
+
+// soft layout (doubles): per-stage constraint vectors, then the flat Qx / qx | Zl / zl block in the reference's
+// carve order with its padding (d_ip2_soft.c:244-260)
+const char* soft_layout(int N, const int* nx, const int* nu, const int* nb, const int* ns, SoftLayout& L) {
+    std::vector<SoftStage>& ss = L.st;
+    ss.assign(N + 1, SoftStage());
+    long sC = 0, sD = 0, sZ = 0, F = 0;
+    int padM = 0;
+    for (int k = 0; k <= N; k++) {
+        SoftStage& s = ss[k];
+        memset(&s, 0, sizeof s);
+        s.nu = k < N ? nu[k] : 0;
+        s.nx = nx[k];
+        s.nx1 = k < N ? nx[k + 1] : 0;
+        s.nb = nb[k];
+        s.ns = ns[k];
+        s.pnb = rup(nb[k], BS);
+        s.pns = rup(ns[k], BS);
+        s.oC = (int)sC;
+        sC += 2 * s.pnb + 4 * s.pns;
+        s.oD = (int)sD;
+        sD += 2 * s.pnb + 2 * s.pns;
+        s.oZ = (int)sZ;
+        sZ += 2 * s.pns;
+        s.oQ = (int)F;
+        F += 2 * (s.pnb + s.pns);
+        padM = std::max(padM, 2 * (s.pnb + s.pns));
+    }
+    for (int k = 0; k <= N; k++) {
+        ss[k].oZl = (int)F;
+        F += 4 * ss[k].pns;
+    }
+    L.sC = sC;
+    L.sD = sD;
+    L.sZ = sZ;
+    L.sF = F + padM + 16;
+    for (int k = 0; k <= N; k++) {  // where the soft gradient term goes (d_aux_ip_soft_lib4.c:557, :601)
+        SoftStage& s = ss[k];
+        const int pnbs = rup(s.nb + s.ns, BS);
+        s.oS = s.oQ + s.pnb + s.pns + (s.nb > 0 ? pnbs + s.nb : s.nb);
+        for (int i = 0; s.nb > 0 && i < s.ns; i++)
+            for (int j = k; j <= N; j++)
+                if (s.oS + i >= ss[j].oZl && s.oS + i < ss[j].oZl + 2 * ss[j].pns)
+                    return "soft IPM: the reference's soft-gradient write lands in a Zl read later in the same pass";
+    }
+    return nullptr;
+}
+
+namespace {
 
 bool soft_launch(int which, const SoftArgs& s) {
     if (hk_soft_launch(which, &s, 1, g_dev.stream)) {
@@ -70,47 +116,13 @@ extern "C" int d_ip2_mpc_soft_tv(int* kk, int k_max, double mu0, double mu_tol, 
     for (int k = 0; k <= N; k++) nbs[k] = nb[k] + ns[k];
     hpmpc_mi355x_plan* P = thread_plan(N, nx, nu, nbs.data(), idxb, ng);
     if (!P) return g_err;
-    // soft layout (doubles): per-stage constraint vectors, then the flat Qx / qx | Zl / zl block
-    std::vector<SoftStage> ss(N + 1);
-    long sC = 0, sD = 0, sZ = 0, F = 0;
-    int padM = 0;
-    for (int k = 0; k <= N; k++) {
-        SoftStage& s = ss[k];
-        memset(&s, 0, sizeof s);
-        s.nu = P->st[k].nu;
-        s.nx = nx[k];
-        s.nx1 = k < N ? nx[k + 1] : 0;
-        s.nb = nb[k];
-        s.ns = ns[k];
-        s.pnb = rup(nb[k], BS);
-        s.pns = rup(ns[k], BS);
-        s.oC = (int)sC;
-        sC += 2 * s.pnb + 4 * s.pns;
-        s.oD = (int)sD;
-        sD += 2 * s.pnb + 2 * s.pns;
-        s.oZ = (int)sZ;
-        sZ += 2 * s.pns;
-        s.oQ = (int)F;
-        F += 2 * (s.pnb + s.pns);
-        padM = std::max(padM, 2 * (s.pnb + s.pns));
+    SoftLayout SL;
+    if (const char* why = soft_layout(N, nx, nu, nb, ns, SL)) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, why);
+        return g_err;
     }
-    for (int k = 0; k <= N; k++) {
-        ss[k].oZl = (int)F;
-        F += 4 * ss[k].pns;
-    }
-    const long sF = F + padM + 16;
-    for (int k = 0; k <= N; k++) {  // where the soft gradient term goes (d_aux_ip_soft_lib4.c:557, :601)
-        SoftStage& s = ss[k];
-        const int pnbs = rup(s.nb + s.ns, BS);
-        s.oS = s.oQ + s.pnb + s.pns + (s.nb > 0 ? pnbs + s.nb : s.nb);
-        for (int i = 0; s.nb > 0 && i < s.ns; i++)
-            for (int j = k; j <= N; j++)
-                if (s.oS + i >= ss[j].oZl && s.oS + i < ss[j].oZl + 2 * ss[j].pns) {
-                    hk_set_error(HPMPC_MI355X_EUNSUPPORTED,
-                            "soft IPM: the reference's soft-gradient write lands in a Zl read later in the same pass");
-                    return g_err;
-                }
-    }
+    const std::vector<SoftStage>& ss = SL.st;
+    const long sC = SL.sC, sD = SL.sD, sZ = SL.sZ, sF = SL.sF;
     Arena A = arena(P, 1);
     const size_t n1 = N + 1, v16 = n1 * V16;
     size_t o = A.total;

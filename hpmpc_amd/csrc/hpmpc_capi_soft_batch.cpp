@@ -1,0 +1,217 @@
+// hpmpc_capi_soft_batch.cpp -- the batched, device-resident soft-constraint IPM: hpmpc_mi355x_soft_plan_* and
+// hpmpc_mi355x_ipm_soft_batch, d_ip2_mpc_soft_tv (mpc_solvers/d_ip2_soft.c:83-547) on problems whose arrays are
+// already in HBM, every iteration of every problem in one launch of hk_soft_ipm (hk_soft_ipm.hip).
+//
+// A soft plan wraps a tile plan on nb + ns boxes per stage (the plan the reference-named entry point solves on) and
+// the soft layout; what it refuses, it refuses through the functions that entry point calls (soft_unsupported,
+// soft_layout, plan_supported).  Per problem the caller passes d, Z / z, lam / t in the reference's per-stage
+// layouts at the offsets of hpmpc_mi355x_soft_offsets, ux / pi with 16 doubles per stage, and a workspace:
+//   [ factor (N+1) FSTRIDE | dux dpi b q Qx qx Pb, (N+1) 16 each | dt dlam lamt tinv | flat Qx qx Zl zl | scal | ist ]
+// (the flat block in the reference's carve order with its padding, hk_soft_args.h).
+#include "hk_launch_guard.h"
+#include "hk_plan.h"
+
+struct hpmpc_mi355x_soft_plan {
+    hpmpc_mi355x_plan* tile = nullptr;
+    int N = 0;
+    SoftLayout L;
+    double mu_scal = 0.0;  // 1 / sum(2 nb + 4 ns); 0: no constraint anywhere
+    // workspace carve (doubles)
+    long long oV16 = 0, oCv = 0, nCv = 0, oFlat = 0, oScal = 0, oIst = 0, ws = 0;
+    SoftStage* d_st = nullptr;
+    int* d_idx = nullptr;
+};
+
+extern "C" void hpmpc_mi355x_soft_plan_destroy(hpmpc_mi355x_soft_plan* S) {
+    if (!S) return;
+    if (S->tile) hpmpc_mi355x_plan_destroy(S->tile);
+    if (S->d_st) (void)hipFree(S->d_st);
+    if (S->d_idx) (void)hipFree(S->d_idx);
+    delete S;
+}
+
+extern "C" hpmpc_mi355x_soft_plan* hpmpc_mi355x_soft_plan_create(int N, const int* nx, const int* nu, const int* nb,
+                                                                 const int* const* idxb, const int* ng,
+                                                                 const int* ns) {
+    g_err = 0;
+    if (const char* why = soft_unsupported(N, nx, nu, ng)) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, why);
+        return nullptr;
+    }
+    std::vector<int> nbs(N + 1);
+    for (int k = 0; k <= N; k++) {
+        if (nb[k] < 0 || ns[k] < 0) {
+            hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "soft IPM: nb[k], ns[k] >= 0 required");
+            return nullptr;
+        }
+        nbs[k] = nb[k] + ns[k];
+    }
+    auto* S = new hpmpc_mi355x_soft_plan();
+    S->N = N;
+    S->tile = hpmpc_mi355x_plan_create(N, nx, nu, nbs.data(), idxb, ng);  // tile limits, round_up(nb + ns, 4) <= 16
+    if (!S->tile) {
+        hpmpc_mi355x_soft_plan_destroy(S);
+        return nullptr;
+    }
+    if (const char* why = soft_layout(N, nx, nu, nb, ns, S->L)) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, why);
+        hpmpc_mi355x_soft_plan_destroy(S);
+        return nullptr;
+    }
+    double m = 0.0;
+    for (int k = 0; k <= N; k++) m += 2 * nb[k] + 4 * ns[k];
+    S->mu_scal = m > 0.0 ? 1.0 / m : 0.0;
+    const long long n1 = N + 1;
+    auto r8 = [](long long n) { return (n + 7) / 8 * 8; };
+    long long o = n1 * FSTRIDE;
+    S->oV16 = o;
+    o += 7 * n1 * V16;
+    S->oCv = o;
+    S->nCv = r8(S->L.sC + 1);
+    o += 4 * S->nCv;
+    S->oFlat = o;
+    o += r8(S->L.sF);
+    S->oScal = o;
+    o += 8;
+    S->oIst = o;
+    o += 8;
+    S->ws = (o + 31) / 32 * 32;  // 256-byte granules: every problem's arrays keep their cache-line alignment
+    std::vector<int> idx(n1 * 16, 0);
+    for (int k = 0; k <= N; k++)
+        for (int l = 0; l < nbs[k]; l++) idx[k * 16 + l] = idxb[k][l];
+    const bool ok = hip_ok(hipMalloc((void**)&S->d_st, sizeof(SoftStage) * n1), "soft plan alloc") &&
+                    hip_ok(hipMalloc((void**)&S->d_idx, sizeof(int) * 16 * n1), "soft plan alloc") &&
+                    hip_ok(hipMemcpy(S->d_st, S->L.st.data(), sizeof(SoftStage) * n1, hipMemcpyHostToDevice),
+                           "soft plan") &&
+                    hip_ok(hipMemcpy(S->d_idx, idx.data(), sizeof(int) * 16 * n1, hipMemcpyHostToDevice), "soft plan");
+    if (!ok) {
+        hpmpc_mi355x_soft_plan_destroy(S);
+        return nullptr;
+    }
+    g_err = 0;
+    return S;
+}
+
+// out[6]: doubles per problem of d, Z (= z), lam (= t), ux (= pi), the workspace; N
+extern "C" int hpmpc_mi355x_soft_sizes(const hpmpc_mi355x_soft_plan* S, long long* out) {
+    if (!S || !out) return HPMPC_MI355X_EUNSUPPORTED;
+    const long long v[6] = {S->L.sD, S->L.sZ, S->L.sC, (long long)(S->N + 1) * V16, S->ws, S->N};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+// out[3*(N+1)]: oD, oZ, oC of every stage (doubles inside one problem's d, Z / z, lam / t)
+extern "C" int hpmpc_mi355x_soft_offsets(const hpmpc_mi355x_soft_plan* S, long long* out) {
+    if (!S || !out) return HPMPC_MI355X_EUNSUPPORTED;
+    for (int k = 0; k <= S->N; k++) {
+        const SoftStage& s = S->L.st[k];
+        out[3 * k] = s.oD;
+        out[3 * k + 1] = s.oZ;
+        out[3 * k + 2] = s.oC;
+    }
+    return 0;
+}
+
+// d_ip2_mpc_soft_tv on problems [p0, p0 + count) of a device-resident batch.  Asynchronous on `stream`: two launches
+// (hk_soft_ipm_init, hk_soft_ipm), no synchronisation (a layout's first use uploads its stage table, layout_apply).
+extern "C" int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan* S, const hpmpc_mi355x_layout* lay, int nprob,
+                                           int p0, int count, const double* BAbt, const double* RSQrq,
+                                           const double* Z, const double* z, const double* d, double* ux, double* pi,
+                                           double* lam, double* t, double* ws, int k_max, double mu0, double mu_tol,
+                                           double alpha_min, int warm_start, int compute_mult, int* kk, int* ret,
+                                           double* stat, void* stream) {
+    g_err = 0;
+    if (!S || nprob <= 0 || p0 < 0 || count < 0 || p0 + count > nprob || k_max < 0 || !kk || !ret) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ipm_soft_batch: plan, problem range or k_max");
+        return g_err;
+    }
+    if (count == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (S->mu_scal == 0.0) {
+        // no constraint anywhere: the reference solves into its workspace and leaves every output but kk untouched
+        // (d_ip2_soft.c:273-284); kk = 0, ret = 0
+        if (!hip_ok(hipMemsetAsync(kk + p0, 0, sizeof(int) * count, st), "memset kk") ||
+            !hip_ok(hipMemsetAsync(ret + p0, 0, sizeof(int) * count, st), "memset ret"))
+            return g_err;
+        return 0;
+    }
+    const bool soft = S->L.sZ > 0;
+    if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !ws || (k_max > 0 && !stat) || (soft && (!Z || !z))) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ipm_soft_batch: a required array is null");
+        return g_err;
+    }
+    hpmpc_mi355x_plan* P = S->tile;
+    const int N = S->N;
+    const long long n1 = N + 1, v16 = n1 * V16;
+    KArgs a = base_args(P, nprob, p0);
+    if (!layout_apply(P, lay, a)) return g_err;
+    a.BAbt = BAbt;
+    a.RSQ = RSQrq;
+    a.ws = ws;
+    a.sW = S->ws;
+    a.sV16 = S->ws;  // the Riccati vectors live in the workspace
+    double* V = ws + S->oV16;
+    a.ux = V;  // the Riccati solution: the step's target dux / dpi
+    a.pi = V + v16;
+    a.vb = V + 2 * v16;
+    a.vq = V + 3 * v16;
+    a.vQx = V + 4 * v16;
+    a.vqx = V + 5 * v16;
+    a.vPb = V + 6 * v16;
+    a.use_box = 1;
+    a.update_q = 1;
+    a.update_b = 0;
+    a.compute_pi = compute_mult;
+    a.compute_Pb = 1;
+    a.k_max = k_max;
+    SoftArgs s;
+    memset(&s, 0, sizeof s);
+    s.N = N;
+    s.nprob = nprob;
+    s.p0 = p0;
+    s.k_max = k_max;
+    s.warm_start = warm_start;
+    s.nq = (N + 4) / 4;
+    s.st = S->d_st;
+    s.idxb = S->d_idx;
+    s.d = d;
+    s.Z = Z;
+    s.z = z;
+    s.sD = S->L.sD;
+    s.sZ = S->L.sZ;
+    s.t = t;
+    s.lam = lam;
+    s.sC = S->L.sC;
+    s.ux = ux;
+    s.pi = pi;
+    s.sV = v16;
+    double* Cv = ws + S->oCv;
+    s.dt = Cv;
+    s.dlam = Cv + S->nCv;
+    s.lamt = Cv + 2 * S->nCv;
+    s.tinv = Cv + 3 * S->nCv;
+    s.flat = ws + S->oFlat;
+    s.dux = V;
+    s.dpi = V + v16;
+    s.vb = V + 2 * v16;
+    s.vq = V + 3 * v16;
+    s.vQx = V + 4 * v16;
+    s.vqx = V + 5 * v16;
+    s.scal = ws + S->oScal;
+    s.ist = reinterpret_cast<int*>(ws + S->oIst);
+    s.sW = S->ws;
+    s.mu0 = mu0;
+    s.mu_tol = mu_tol;
+    s.alpha_min = alpha_min;
+    s.mu_scal = S->mu_scal;
+    s.stat = stat;
+    s.sS = 5LL * k_max;
+    s.kk = kk;
+    s.ret = ret;
+    if (const int e = hk_soft_ipm_launch(&a, &s, count, st)) {
+        hk_set_error(e == HK_LAUNCH_REFUSED ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP,
+                     "hk_soft_ipm launch failed");
+        return g_err;
+    }
+    return g_err = 0;
+}

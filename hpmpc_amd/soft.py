@@ -134,3 +134,285 @@ def mass_spring_soft(N: int, nx: int, nu: int, *, x0=None, Zq: float = 0.0, zl: 
         Zv.append(Zk)
         zv.append(zk)
     return SoftQP(N, nxv, nuv, nbv, nsv, idxb, BAbt, RSQrq, dv, Zv, zv)
+
+
+# ------------------------------------------------------------------------------------------------
+# Batched, device-resident soft-constraint IPM (hpmpc_mi355x_ipm_soft_batch, include/hpmpc_mi355x.h): a batch is
+# a list of SoftQPs that share stage sizes and idxb.  Problem-major arrays, every stage in the reference's layout:
+#   BAbt  (P, packB)  lib4 blocks, stage k at offB[k]        RSQrq (P, packR)  stage k at offR[k]
+#   d     (P, sD)     [lb pnb | ub pnb | ls pns | us pns] at oD[k]
+#   Z, z  (P, sZ)     [lower pns | upper pns] at oZ[k]
+#   lam,t (P, sC)     [lo pnb | up pnb | 4 x pns] at oC[k]
+#   ux,pi (P, N+1, 16)
+# ------------------------------------------------------------------------------------------------
+FSTRIDE = 352  # factor doubles per stage (hpmpc_amd/csrc/hpmpc_kargs.h)
+
+
+def soft_batch_layout(sq: SoftQP) -> dict:
+    """Per-stage offsets oD / oZ / oC (doubles inside one problem's d, Z / z, lam / t) and the per-problem sizes
+    (d, Z, C, ux, ws, N) of the batched soft IPM: what hpmpc_mi355x_soft_offsets / _sizes return.  Pure."""
+    N = sq.N
+    oD, oZ, oC = (np.zeros(N + 1, dtype=np.int64) for _ in range(3))
+    sD = sZ = sC = F = padM = 0
+    for k in range(N + 1):
+        pnb, pns = rup(int(sq.nb[k]), 4), rup(int(sq.ns[k]), 4)
+        oD[k], oZ[k], oC[k] = sD, sZ, sC
+        sD += 2 * pnb + 2 * pns
+        sZ += 2 * pns
+        sC += 2 * pnb + 4 * pns
+        F += 2 * (pnb + pns) + 4 * pns  # Qx, qx of every stage, then Zl, zl of every stage
+        padM = max(padM, 2 * (pnb + pns))
+    n1 = N + 1
+    # workspace: factor | 7 vectors of 16 per stage | dt dlam lamt tinv | flat block (reference padding) | scal | ist
+    ws = n1 * FSTRIDE + 7 * n1 * 16 + 4 * rup(sC + 1, 8) + rup(F + padM + 16, 8) + 8 + 8
+    return dict(oD=oD, oZ=oZ, oC=oC, sizes=dict(d=sD, Z=sZ, C=sC, ux=n1 * 16, ws=rup(ws, 32), N=N))
+
+
+def _same_shape(sqs):
+    t = sqs[0]
+    for s in sqs[1:]:
+        ok = s.N == t.N and all(np.array_equal(getattr(s, f), getattr(t, f)) for f in ("nx", "nu", "nb", "ns", "ng"))
+        ok = ok and all(np.array_equal(a[:int(t.nb[k] + t.ns[k])], b[:int(t.nb[k] + t.ns[k])])
+                        for k, (a, b) in enumerate(zip(s.idxb, t.idxb)))
+        if not ok:
+            raise ValueError("the problems of a batch share stage sizes and idxb")
+
+
+def pack_soft_batch(sqs) -> dict:
+    """Problem-major host arrays of a list of SoftQPs (shared sizes and idxb): BAbt, RSQrq, d, Z, z, the stage
+    offsets offB / offR of the lib4 blocks and the soft layout (soft_batch_layout)."""
+    _same_shape(sqs)
+    t = sqs[0]
+    N, P = t.N, len(sqs)
+    lay = soft_batch_layout(t)
+    sz = lay["sizes"]
+    offB = np.concatenate([[0], np.cumsum([t.BAbt[k].size for k in range(N)])]).astype(np.int64)
+    offR = np.concatenate([[0], np.cumsum([t.RSQrq[k].size for k in range(N + 1)])]).astype(np.int64)
+    hB = np.stack([np.concatenate([np.asarray(s.BAbt[k], dtype=np.float64).ravel() for k in range(N)]) for s in sqs])
+    hR = np.stack([np.concatenate([np.asarray(s.RSQrq[k], dtype=np.float64).ravel() for k in range(N + 1)])
+                   for s in sqs])
+    hd, hZ, hz = np.zeros((P, sz["d"])), np.zeros((P, sz["Z"])), np.zeros((P, sz["Z"]))
+    for p, s in enumerate(sqs):
+        for k in range(N + 1):
+            pnb, pns = rup(int(t.nb[k]), 4), rup(int(t.ns[k]), 4)
+            n = 2 * pnb + 2 * pns
+            hd[p, lay["oD"][k]:lay["oD"][k] + n] = s.d[k][:n]
+            hZ[p, lay["oZ"][k]:lay["oZ"][k] + 2 * pns] = s.Z[k][:2 * pns]
+            hz[p, lay["oZ"][k]:lay["oZ"][k] + 2 * pns] = s.z[k][:2 * pns]
+    return dict(BAbt=hB, RSQrq=hR, d=hd, Z=hZ, z=hz, offB=offB[:N], offR=offR[:N + 1], packB=int(offB[-1]),
+                packR=int(offR[-1]), layout=lay)
+
+
+def unpack_soft_batch(template: SoftQP, packed: dict) -> list:
+    """Inverse of pack_soft_batch: the SoftQPs whose sizes / idxb are the template's and whose data are the packed
+    arrays (the vectors keep the template's padded lengths; the padding is zero)."""
+    N, lay = template.N, packed["layout"]
+    out = []
+    for p in range(packed["BAbt"].shape[0]):
+        s = template.copy()
+        for k in range(N + 1):
+            if k < N:
+                s.BAbt[k] = packed["BAbt"][p, packed["offB"][k]:packed["offB"][k] + template.BAbt[k].size].copy()
+            s.RSQrq[k] = packed["RSQrq"][p, packed["offR"][k]:packed["offR"][k] + template.RSQrq[k].size].copy()
+            pnb, pns = rup(int(template.nb[k]), 4), rup(int(template.ns[k]), 4)
+            n = 2 * pnb + 2 * pns
+            s.d[k] = np.zeros_like(template.d[k])
+            s.d[k][:n] = packed["d"][p, lay["oD"][k]:lay["oD"][k] + n]
+            s.Z[k] = np.zeros_like(template.Z[k])
+            s.z[k] = np.zeros_like(template.z[k])
+            s.Z[k][:2 * pns] = packed["Z"][p, lay["oZ"][k]:lay["oZ"][k] + 2 * pns]
+            s.z[k][:2 * pns] = packed["z"][p, lay["oZ"][k]:lay["oZ"][k] + 2 * pns]
+        out.append(s)
+    return out
+
+
+def unpack_soft_solution(template: SoftQP, ux, pi, lam, t, kk, ret, stat) -> list:
+    """Per-problem results of a batched solve, shaped like HpmpcAPI.ipm_soft's: dicts of ret, kk, stat (5 kk) and the
+    per-stage lists ux (nu + nx), pi (nx[k+1]), lam / t (2 pnb + 4 pns).  Arrays: host (numpy) copies of the
+    solver's ux / pi (P, N+1, 16), lam / t (P, sC), kk / ret (P), stat (P, 5 k_max)."""
+    N, lay = template.N, soft_batch_layout(template)
+    out = []
+    for p in range(len(kk)):
+        k_it = int(kk[p])
+        r = dict(ret=int(ret[p]), kk=k_it, stat=np.array(stat[p, :5 * max(k_it, 0)], copy=True), ux=[], pi=[], lam=[],
+                 t=[])
+        for k in range(N + 1):
+            r["ux"].append(np.array(ux[p, k, :template.nux(k)], copy=True))
+            if k < N:
+                r["pi"].append(np.array(pi[p, k, :int(template.nx[k + 1])], copy=True))
+            o, n = int(lay["oC"][k]), template.ncv(k)
+            r["lam"].append(np.array(lam[p, o:o + n], copy=True))
+            r["t"].append(np.array(t[p, o:o + n], copy=True))
+        out.append(r)
+    return out
+
+
+def _soft_lib():
+    import ctypes as C
+
+    from .batch import lib
+
+    L = lib()
+    if not getattr(L, "_soft_bound", False):
+        vp, i, d = C.c_void_p, C.c_int, C.c_double
+        L.hpmpc_mi355x_soft_plan_create.restype = vp
+        L.hpmpc_mi355x_soft_plan_create.argtypes = [i, vp, vp, vp, vp, vp, vp]
+        L.hpmpc_mi355x_soft_plan_destroy.argtypes = [vp]
+        L.hpmpc_mi355x_soft_sizes.restype = i
+        L.hpmpc_mi355x_soft_sizes.argtypes = [vp, vp]
+        L.hpmpc_mi355x_soft_offsets.restype = i
+        L.hpmpc_mi355x_soft_offsets.argtypes = [vp, vp]
+        L.hpmpc_mi355x_ipm_soft_batch.restype = i
+        L.hpmpc_mi355x_ipm_soft_batch.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d,
+                                                  i, i, vp, vp, vp, vp]
+        L._soft_bound = True
+    return L
+
+
+def soft_plan_create(sq: SoftQP):
+    """hpmpc_mi355x_soft_plan_create on a SoftQP's sizes.  Returns (plan or None, last error code)."""
+    import ctypes as C
+
+    L = _soft_lib()
+    N = sq.N
+    iv = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    nx, nu, nb, ng, ns = iv(sq.nx), iv(sq.nu), iv(sq.nb), iv(sq.ng), iv(sq.ns)
+    idx = [iv(a) for a in sq.idxb]
+    idxp = (C.POINTER(C.c_int) * (N + 1))(*[a.ctypes.data_as(C.POINTER(C.c_int)) for a in idx])
+    plan = L.hpmpc_mi355x_soft_plan_create(N, nx.ctypes.data, nu.ctypes.data, nb.ctypes.data,
+                                           C.cast(idxp, C.c_void_p), ng.ctypes.data, ns.ctypes.data)
+    return (plan or None), int(L.hpmpc_mi355x_last_error())
+
+
+class SoftBatchSolver:
+    """Device-resident batch of soft-constrained QPs + hpmpc_mi355x_ipm_soft_batch: every iteration of every problem
+    in one launch on torch's current stream (torch is plumbing: allocation and streams).  There is no CPU fallback.
+
+    ``shared=True`` keeps one copy of the BAbt / RSQrq blocks of stages >= 1 for the whole batch (they must be equal
+    in every problem) and stage 0 per problem, through hpmpc_mi355x_layout's shared flags."""
+
+    def __init__(self, sqs, k_max: int = 50, device="cuda", shared: bool = False):
+        import ctypes as C
+
+        import torch
+
+        from .batch import _Layout
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("SoftBatchSolver needs a GPU (HIP device); there is no CPU fallback")
+        self.torch = torch
+        self.sqs = list(sqs)
+        self.template = t = self.sqs[0]
+        self.N, self.nprob, self.k_max = t.N, len(self.sqs), int(k_max)
+        self.dev = torch.device(device)
+        L = _soft_lib()
+        pk = pack_soft_batch(self.sqs)
+        self.plan, err = soft_plan_create(t)
+        if not self.plan:
+            raise ValueError(f"unsupported problem for the batched soft IPM (code {err})")
+        sz = (C.c_longlong * 6)()
+        L.hpmpc_mi355x_soft_sizes(self.plan, sz)
+        self.sizes = dict(zip(("d", "Z", "C", "ux", "ws", "N"), (int(v) for v in sz)))
+        off = (C.c_longlong * (3 * (self.N + 1)))()
+        L.hpmpc_mi355x_soft_offsets(self.plan, off)
+        self.offsets = np.array(off[:], dtype=np.int64).reshape(self.N + 1, 3)  # oD oZ oC
+        N, P, f64 = self.N, self.nprob, torch.float64
+        hB, hR, offB, offR = pk["BAbt"], pk["RSQrq"], pk["offB"].copy(), pk["offR"].copy()
+        sB, sR, shB, shR = pk["packB"], pk["packR"], None, None
+        if shared:
+            if not ((hB[:, offB[1] if N > 1 else sB:] == hB[:1, offB[1] if N > 1 else sB:]).all()
+                    and (hR[:, offR[1]:] == hR[:1, offR[1]:]).all()):
+                raise ValueError("stage data beyond stage 0 differ between problems")
+            b0, r0 = int(offB[1]) if N > 1 else sB, int(offR[1])
+            # [blocks of stages >= 1, once | stage 0 of problem 0 | stage 0 of problem 1 | ...]
+            offB = np.array([sB - b0] + [int(o) - b0 for o in offB[1:]], dtype=np.int64)
+            offR = np.array([sR - r0] + [int(o) - r0 for o in offR[1:]], dtype=np.int64)
+            hB = np.concatenate([hB[0, b0:], hB[:, :b0].reshape(-1)])
+            hR = np.concatenate([hR[0, r0:], hR[:, :r0].reshape(-1)])
+            sB, sR = b0, r0
+            shB = np.array([0] + [1] * (N - 1), dtype=np.uint8)
+            shR = np.array([0] + [1] * N, dtype=np.uint8)
+        self._keep = (offB, offR, shB, shR)
+        ll, u8 = C.POINTER(C.c_longlong), C.POINTER(C.c_ubyte)
+        self.layout = _Layout(sB, sR, offB.ctypes.data_as(ll), offR.ctypes.data_as(ll),
+                              shB.ctypes.data_as(u8) if shared else None, shR.ctypes.data_as(u8) if shared else None)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        self.BAbt, self.RSQrq = up(hB), up(hR)
+        self.d, self.Z, self.z = up(pk["d"]), up(pk["Z"]), up(pk["z"])
+        self.ux = torch.zeros((P, N + 1, 16), dtype=f64, device=self.dev)
+        self.pi = torch.zeros((P, N + 1, 16), dtype=f64, device=self.dev)
+        self.lam = torch.zeros((P, self.sizes["C"]), dtype=f64, device=self.dev)
+        self.t = torch.zeros((P, self.sizes["C"]), dtype=f64, device=self.dev)
+        self.ws = torch.empty((P, self.sizes["ws"]), dtype=f64, device=self.dev)  # needs no initialisation
+        self.kk = torch.zeros(P, dtype=torch.int32, device=self.dev)
+        self.ret = torch.zeros(P, dtype=torch.int32, device=self.dev)
+        self.stat = torch.zeros((P, 5 * max(self.k_max, 1)), dtype=f64, device=self.dev)
+
+    def __del__(self):
+        try:
+            if getattr(self, "plan", None):
+                _soft_lib().hpmpc_mi355x_soft_plan_destroy(self.plan)
+        except Exception:
+            pass
+
+    def set_ux(self, ux0):
+        """Warm-start iterate: ux0[p][k] holds at least nu + nx values of problem p, stage k."""
+        h = np.zeros((self.nprob, self.N + 1, 16))
+        for p in range(self.nprob):
+            for k in range(self.N + 1):
+                n = self.template.nux(k)
+                h[p, k, :n] = np.asarray(ux0[p][k])[:n]
+        self.ux.copy_(self.torch.from_numpy(h))
+
+    def solve(self, *, k_max=None, mu0=100.0, mu_tol=1e-8, alpha_min=1e-8, warm_start=0, compute_mult=1, p0=0,
+              count=None):
+        """Batched d_ip2_mpc_soft_tv on problems [p0, p0 + count), asynchronous on torch's current stream.
+        k_max: at most the solver's (its stat rows are 5 k_max wide)."""
+        import ctypes as C
+
+        k_max = self.k_max if k_max is None else int(k_max)
+        assert 0 <= k_max <= self.k_max
+        count = self.nprob - p0 if count is None else count
+        # stat keeps the stride the call uses: 5 k_max per problem
+        stat = self.stat if k_max == self.k_max else self.stat.view(-1)[:self.nprob * 5 * max(k_max, 1)]
+        self._stat_kmax = k_max
+        rc = _soft_lib().hpmpc_mi355x_ipm_soft_batch(
+            self.plan, C.byref(self.layout), self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
+            self.Z.data_ptr(), self.z.data_ptr(), self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(),
+            self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(), k_max, mu0, mu_tol, alpha_min, warm_start,
+            compute_mult, self.kk.data_ptr(), self.ret.data_ptr(), stat.data_ptr(),
+            self.torch.cuda.current_stream(self.dev).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"hpmpc_mi355x_ipm_soft_batch failed ({rc})")
+
+    def results(self) -> list:
+        """Synchronise and return the per-problem dicts of unpack_soft_solution."""
+        self.torch.cuda.synchronize(self.dev)
+        k_max = getattr(self, "_stat_kmax", self.k_max)
+        stat = self.stat.view(-1)[:self.nprob * 5 * max(k_max, 1)].view(self.nprob, -1).cpu().numpy()
+        c = lambda x: x.cpu().numpy()
+        return unpack_soft_solution(self.template, c(self.ux), c(self.pi), c(self.lam), c(self.t), c(self.kk),
+                                    c(self.ret), stat)
+
+
+def soft_algorithmic_bytes_per_ip_iter(sq: SoftQP) -> float:
+    """Algorithmic HBM bytes of one iteration of one problem through hk_soft_ipm, each datum counted
+    once per body, T = nux (nux + 1) / 2:
+    - Riccati sv: BAbt with its b row, lower(RSQrq), q, Qx / qx slots read; L lower + row + inv_diag, P b, dux, dpi
+      written.  Riccati trs: L, BAbt, b, q, qx slots, P b read; dux, dpi written;
+    - constraint passes per hard box pair: hess 16, pred 20, corr 19 doubles; per soft box (four slack blocks):
+      hess 34, pred 42, corr 39 (t, lam, dt, dlam, lamt, tinv, d, Z, z, Zl, zl, the Qx / qx slots and their flat twins);
+    - corr: ux, dux read and ux written (3 nux), the same for pi (3 nx')."""
+    tot = 0
+    N = sq.N
+    for k in range(N + 1):
+        nux = sq.nux(k)
+        nx1 = int(sq.nx[k + 1]) if k < N else 0
+        nb, ns = int(sq.nb[k]), int(sq.ns[k])
+        T = nux * (nux + 1) // 2
+        L = T + 2 * nux
+        babt = (nux + 1) * nx1
+        sv = babt + T + nux + 2 * (nb + ns) + L + nx1 + nux + nx1
+        trs = L + babt + (nux + nx1) + (nb + ns) + nx1 + (nux + nx1)
+        tot += sv + trs + 55 * nb + 115 * ns + 3 * nux + 3 * nx1
+    return 8.0 * tot

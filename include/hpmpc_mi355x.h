@@ -437,6 +437,40 @@ int hpmpc_mi355x_wide_ipm_batch(const hpmpc_mi355x_wide_plan *plan, int nprob, i
  * IPM on a partially condensed batch (the c_interface wrappers' N2 < N path, batched) */
 const hpmpc_mi355x_wide_plan *hpmpc_mi355x_pcond_wide_plan(const hpmpc_mi355x_pcond_plan *plan);
 
+/* ---- the soft-constraint IPM for device-resident batches ----
+ * d_ip2_mpc_soft_tv (mpc_solvers/d_ip2_soft.c:83) on a batch of problems that share stage sizes and box indices and
+ * whose arrays are already in HBM: one wavefront per problem runs every iteration (Hessian update, Riccati
+ * factorisation and solve, predictor, Riccati solve, corrector) in ONE launch after a short init launch, with no
+ * host poll; a problem that meets its exit test retires its wavefront.  The arithmetic is the reference-named
+ * entry point's (the same device routines), fused: results agree with it to rounding, with the same kk and ret on
+ * every tested problem.
+ * Plan: idxb[k] lists the nb[k] hard boxes, then the ns[k] soft ones.  Refused (NULL, hpmpc_mi355x_last_error() =
+ * HPMPC_MI355X_EUNSUPPORTED) exactly where d_ip2_mpc_soft_tv is: ng > 0, nu[N] != 0, a b_k the reference reads outside
+ * BAbt_k, a stray soft-gradient write into a live Zl, round_up(nb + ns, 4) > 16, stages beyond the 16-wide tile.
+ * Arrays (device pointers, problem-major, per-problem sizes from hpmpc_mi355x_soft_sizes, stage offsets from
+ * hpmpc_mi355x_soft_offsets), each stage in the reference's layout:
+ *   d      [lb pnb | ub pnb | ls pns | us pns] at oD[k]       Z, z   [lower pns | upper pns] at oZ[k]
+ *   lam, t [lo pnb | up pnb | 4 x pns] at oC[k]               ux, pi 16 doubles per stage (as hpmpc_mi355x_ipm_batch)
+ * BAbt / RSQrq follow `lay` as in hpmpc_mi355x_ipm_batch (NULL: the packed default; shared blocks allowed).  ws: the
+ * per-problem workspace (factor, step vectors, dt / dlam / lamt / tinv, the reference's flat Qx | qx | Zl | zl block,
+ * loop state); it needs no initialisation.  kk, ret per problem; stat 5*k_max per problem.  Only problems
+ * [p0, p0+count) are read or written.  Asynchronous on `stream`; nothing in the call synchronises with the device
+ * (the first use of a layout uploads its stage table, as for every batched call).  With no constraint on any stage
+ * kk[p] = 0, ret[p] = 0 and nothing else is written, as in the reference (d_ip2_soft.c:273-284). */
+typedef struct hpmpc_mi355x_soft_plan hpmpc_mi355x_soft_plan;
+hpmpc_mi355x_soft_plan *hpmpc_mi355x_soft_plan_create(int N, const int *nx, const int *nu, const int *nb,
+                                                      const int *const *idxb, const int *ng, const int *ns);
+void hpmpc_mi355x_soft_plan_destroy(hpmpc_mi355x_soft_plan *plan);
+/* out[6]: doubles per problem of d, Z (= z), lam (= t), ux (= pi), ws; N */
+int hpmpc_mi355x_soft_sizes(const hpmpc_mi355x_soft_plan *plan, long long *out);
+/* out[3*(N+1)]: oD, oZ, oC per stage */
+int hpmpc_mi355x_soft_offsets(const hpmpc_mi355x_soft_plan *plan, long long *out);
+int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan *plan, const hpmpc_mi355x_layout *lay, int nprob,
+                                int p0, int count, const double *BAbt, const double *RSQrq, const double *Z,
+                                const double *z, const double *d, double *ux, double *pi, double *lam, double *t,
+                                double *ws, int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
+                                int compute_mult, int *kk, int *ret, double *stat, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

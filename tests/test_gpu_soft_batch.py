@@ -1,0 +1,192 @@
+"""Batched, device-resident soft-constraint IPM (hpmpc_mi355x_ipm_soft_batch, hk_soft_ipm) against the oracle.
+
+Every comparison is per problem, against oracle.ipm_soft with k_max=50, mu0=100, mu_tol=1e-6, alpha_min=1e-8 at
+helpers.TOL_SOFT (ux / t 5e-8, pi / lam 1e-6, stat 1e-7, relative to max(1, |ref|); kk and ret identical) -- the
+comparison of tests/test_gpu_soft.py.  The batches were chosen so that the oracle's own rounding spread (its default
+build against its FMA build) stays under those gates on every gated vector (worst case 12 % of the stat gate); the
+oracle's iteration counts are pinned below, so a change of the inputs shows up as such.  Problem i of a batch has
+x0[0] = x0[1] = s_i.
+"""
+import numpy as np
+import pytest
+
+from helpers import TOL_SOFT
+from hpmpc_amd.soft import (SoftBatchSolver, mass_spring_soft, soft_batch_layout, soft_plan_create)
+from test_gpu_soft import _cmp
+
+pytestmark = pytest.mark.gpu
+EUNSUPPORTED = -10
+ARGS = dict(k_max=50, mu0=100.0, mu_tol=1e-6, alpha_min=1e-8)
+S5 = (0.2, 1.0, 2.0, 3.5, 6.0)
+
+
+def _batch(scales, seeds=None, **mk):
+    out = []
+    for i, s in enumerate(scales):
+        x0 = np.zeros(mk["nx"])
+        x0[0] = x0[1] = s
+        kw = dict(mk)
+        if seeds is not None:
+            kw["seed"] = seeds[i]
+        out.append(mass_spring_soft(x0=x0, **kw))
+    return out
+
+
+# name -> (problems, the oracle's iteration counts)
+FAMILIES = {
+    # mixed exit iterations, a partial last stage quad, hard and soft boxes on the last stage
+    "mixed_N4": (lambda: _batch(S5, N=4, nx=4, nu=2, hard_last=2, Q_diag=1.0), [5, 6, 8, 6, 6]),
+    # time-variant data: every stage block differs between problems
+    "tv_N8": (lambda: _batch(S5, seeds=[3 + i for i in range(5)], N=8, nx=8, nu=3, time_variant=True, Q_diag=1.0,
+                             Zq=2.0, zl=5.0), [5, 6, 8, 8, 9]),
+    # full tile (nu + nx = 16), the compiled inner-stage class
+    "full_N9": (lambda: _batch((0.2, 1.0, 3.5), N=9, nx=12, nu=4, Q_diag=1.0, Zq=1.0), [5, 6, 10]),
+    # shortest horizon
+    "N1": (lambda: _batch((0.2, 1.0), N=1, nx=4, nu=2, Q_diag=1.0), [5, 6]),
+}
+
+
+@pytest.fixture(scope="module")
+def refs(oracle):
+    """The oracle's solutions, computed once per batch and shared (never modified)."""
+    cache = {}
+
+    def get(name, sqs=None, ux=None, **args):
+        if name not in cache:
+            sqs = FAMILIES[name][0]() if sqs is None else sqs
+            a = dict(ARGS)
+            a.update(args)
+            cache[name] = (sqs, [oracle.ipm_soft(sq.copy(), **a, **({} if ux is None else dict(ux=ux)))
+                                 for sq in sqs])
+        return cache[name]
+
+    return get
+
+
+def _check(sqs, got, ref):
+    assert len(got) == len(ref)
+    for sq, g, r in zip(sqs, got, ref):
+        _cmp(sq, g, r)
+
+
+@pytest.mark.parametrize("name", list(FAMILIES), ids=list(FAMILIES))
+def test_batch_vs_oracle(refs, name):
+    sqs, ref = refs(name)
+    assert [r["kk"] for r in ref] == FAMILIES[name][1], [r["kk"] for r in ref]
+    sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
+    sv.ws.fill_(float("nan"))  # the workspace needs no initialisation
+    sv.solve(**ARGS)
+    got = sv.results()
+    _check(sqs, got, ref)
+    if name == "mixed_N4":  # the waves retire at different iterations
+        assert len({g["kk"] for g in got}) > 1
+
+
+def test_sub_range(refs):
+    sqs, ref = refs("mixed_N4")
+    sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
+    for x in (sv.ux, sv.pi, sv.lam, sv.t, sv.stat):
+        x.fill_(-7.25)
+    sv.kk.fill_(-3)
+    sv.ret.fill_(-3)
+    sv.solve(p0=1, count=3, **ARGS)
+    sv.torch.cuda.synchronize()
+    for p in (0, 4):
+        for x in (sv.ux, sv.pi, sv.lam, sv.t, sv.stat):
+            assert bool((x[p] == -7.25).all())
+        assert int(sv.kk[p]) == -3 and int(sv.ret[p]) == -3
+    got = sv.results()
+    _check(sqs[1:4], got[1:4], ref[1:4])
+
+
+def _stat_err(g, r):
+    assert g["stat"].shape == r["stat"].shape
+    return np.max(np.abs(g["stat"] - r["stat"]) / np.maximum(1.0, np.abs(r["stat"])))
+
+
+def test_exit_k_max(refs):
+    sqs, _ = refs("mixed_N4")
+    _, ref = refs("mixed_N4_kmax3", sqs=sqs, k_max=3)
+    sv = SoftBatchSolver(sqs, k_max=3)
+    a = dict(ARGS, k_max=3)
+    sv.solve(**a)
+    for g, r in zip(sv.results(), ref):
+        assert (g["ret"], g["kk"]) == (1, 3) and (r["ret"], r["kk"]) == (1, 3)
+        assert _stat_err(g, r) <= TOL_SOFT["stat"]
+
+
+def test_exit_alpha_min(refs):
+    sqs, ref = refs("alpha_min_N5", sqs=[mass_spring_soft(N=5, nx=4, nu=2, Q_diag=1.0)], alpha_min=0.9)
+    sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
+    sv.solve(**dict(ARGS, alpha_min=0.9))
+    for g, r in zip(sv.results(), ref):
+        assert (g["ret"], g["kk"]) == (2, 1) and (r["ret"], r["kk"]) == (2, 1)
+        assert _stat_err(g, r) <= TOL_SOFT["stat"]
+
+
+def test_warm_start(refs):
+    sqs = _batch((0.2, 2.0), N=5, nx=4, nu=2, Q_diag=1.0)
+    rng = np.random.default_rng(4)
+    ux0 = [0.05 * rng.standard_normal(sqs[0].nux(k) + 4) for k in range(sqs[0].N + 1)]
+    _, ref = refs("warm_N5", sqs=sqs, ux=ux0, warm_start=1)
+    assert [r["kk"] for r in ref] == [5, 9]
+    sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
+    sv.set_ux([ux0] * len(sqs))
+    sv.solve(warm_start=1, **ARGS)
+    _check(sqs, sv.results(), ref)
+
+
+def test_agrees_with_single_problem_entry_point(product, refs):
+    """kk / ret of d_ip2_mpc_soft_tv per problem; the vectors to TOL_SOFT (the fused kernel may contract products
+    differently, so bitwise equality is not required)."""
+    sqs, _ = refs("mixed_N4")
+    sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
+    sv.solve(**ARGS)
+    got = sv.results()
+    _check(sqs, got, [product.ipm_soft(sq.copy(), **ARGS) for sq in sqs])
+
+
+def test_shared_layout_bitwise(refs):
+    sqs, _ = refs("mixed_N4")
+    out = []
+    for shared in (False, True):
+        sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"], shared=shared)
+        sv.solve(**ARGS)
+        sv.torch.cuda.synchronize()
+        out.append([x.cpu().numpy().copy() for x in (sv.ux, sv.pi, sv.lam, sv.t, sv.kk, sv.ret, sv.stat)])
+    assert out[0][4].max() > 0
+    for a, b in zip(*out):
+        assert np.array_equal(a, b)
+
+
+def test_refusals():
+    plan, err = soft_plan_create(mass_spring_soft(6, 6, 2))  # b_k read outside BAbt_k
+    assert plan is None and err == EUNSUPPORTED
+    sq = mass_spring_soft(6, 8, 2)
+    sq.ng = sq.ng.copy()
+    sq.ng[3] = 1
+    plan, err = soft_plan_create(sq)
+    assert plan is None and err == EUNSUPPORTED
+
+
+def test_no_constraints_leaves_outputs():
+    sqs = [mass_spring_soft(N=5, nx=4, nu=2, soft=False, hard=False)] * 2
+    sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
+    for x in (sv.ux, sv.pi, sv.lam, sv.t, sv.stat):
+        x.fill_(-7.25)
+    sv.kk.fill_(-3)
+    sv.ret.fill_(-3)
+    sv.solve(**ARGS)
+    sv.torch.cuda.synchronize()
+    assert sv.kk.tolist() == [0, 0] and sv.ret.tolist() == [0, 0]
+    for x in (sv.ux, sv.pi, sv.lam, sv.t, sv.stat):
+        assert bool((x == -7.25).all())
+
+
+@pytest.mark.parametrize("name", ["mixed_N4", "full_N9"])
+def test_offsets_and_sizes(refs, name):
+    sqs, _ = refs(name)
+    sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
+    lay = soft_batch_layout(sqs[0])
+    assert sv.sizes == lay["sizes"]
+    assert np.array_equal(sv.offsets, np.stack([lay["oD"], lay["oZ"], lay["oC"]], axis=1))
