@@ -10,6 +10,8 @@ struct KArgs;
 struct SoftArgs;
 struct SoftResArgs;
 struct WideIpmArgs;
+struct OcpPackArgs;
+struct OcpFinishArgs;
 
 extern "C" {
 // hpmpc_kernels.hip: the tile kernels (which: HkLaunch) and the compiled inner-stage class of a stage size
@@ -26,4 +28,7 @@ int hk_soft_ipm_launch(const KArgs* a, const SoftArgs* s, int count, hipStream_t
 // hk_wide.hip (which: HkWideLaunch; args: the WideArgs / PcArgs / PxArgs of that kernel) and hk_wide_ipm.hip
 int hk_wide_launch(int which, const void* args, int count, int lds_doubles, hipStream_t stream);
 int hk_wide_ipm_launch(const WideIpmArgs* a, int count, int lds_doubles, hipStream_t stream);
+// hk_ocp.hip: the batched OCP front end, dense data -> lib4 (grid: stages x a->count problems) and iterate -> outputs
+int hk_ocp_pack_launch(const OcpPackArgs* a, hipStream_t stream);
+int hk_ocp_finish_launch(const OcpFinishArgs* a, hipStream_t stream);
 }

@@ -56,6 +56,10 @@ bool plan_supported(int N, const int* nx, const int* nu, const int* nb, const in
 KArgs base_args(const hpmpc_mi355x_plan* P, int nprob, int p0);
 bool layout_apply(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a);
 int launch(int which, const KArgs* a, int count, hipStream_t s);  // hk_launch, or the ric2 variant's two-wave sv
+// the IPM fields of `a` (plan tables and layout already set) and the launch `which`: shared by every batched IPM call
+int ipm_run(KArgs& a, int count, const double* BAbt, const double* RSQrq, const double* d, double* ux, double* pi,
+            double* lam, double* t, double* ws, int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
+            int compute_mult, int* kk, int* ret, double* stat, int which, void* stream);
 // the calling thread's cached plan for these sizes (created on first use, replaced when the sizes change)
 hpmpc_mi355x_plan* thread_plan(int N, const int* nx, const int* nu, const int* nb, int** idxb, const int* ng);
 

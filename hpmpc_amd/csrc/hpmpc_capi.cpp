@@ -289,16 +289,12 @@ hpmpc_mi355x_plan* thread_plan(int N, const int* nx, const int* nu, const int* n
     return c.plan;
 }
 
-namespace {
-
-int ipm_launch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob, int p0, int count,
-               const double* BAbt, const double* RSQrq, const double* d, double* ux, double* pi, double* lam,
-               double* t, double* ws, int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
-               int compute_mult, int* kk, int* ret, double* stat, int which, void* stream) {
-    auto* P = const_cast<hpmpc_mi355x_plan*>(plan);
-    if (!P) return g_err = HPMPC_MI355X_EUNSUPPORTED;
-    KArgs a = base_args(P, nprob, p0);
-    if (!layout_apply(P, lay, a)) return g_err;
+// The IPM fields of an argument block whose plan tables and layout (st, sB, sR, and DCt / sG for general
+// constraints) are set, then the launch: the body of every batched IPM entry point, hpmpc_mi355x_ocp_ipm_batch
+// (hpmpc_capi_ocp.cpp) included.
+int ipm_run(KArgs& a, int count, const double* BAbt, const double* RSQrq, const double* d, double* ux, double* pi,
+            double* lam, double* t, double* ws, int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
+            int compute_mult, int* kk, int* ret, double* stat, int which, void* stream) {
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
     a.d = d;
@@ -322,6 +318,20 @@ int ipm_launch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, in
         return HPMPC_MI355X_EHIP;
     }
     return g_err = 0;
+}
+
+namespace {
+
+int ipm_launch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob, int p0, int count,
+               const double* BAbt, const double* RSQrq, const double* d, double* ux, double* pi, double* lam,
+               double* t, double* ws, int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
+               int compute_mult, int* kk, int* ret, double* stat, int which, void* stream) {
+    auto* P = const_cast<hpmpc_mi355x_plan*>(plan);
+    if (!P) return g_err = HPMPC_MI355X_EUNSUPPORTED;
+    KArgs a = base_args(P, nprob, p0);
+    if (!layout_apply(P, lay, a)) return g_err;
+    return ipm_run(a, count, BAbt, RSQrq, d, ux, pi, lam, t, ws, k_max, mu0, mu_tol, alpha_min, warm_start,
+                   compute_mult, kk, ret, stat, which, stream);
 }
 
 // hipEvents owned by one API call.  The destructor first waits for every event recorded on them.

@@ -1,0 +1,289 @@
+"""Batched OCP front end: dense problem data in HBM -> pack -> IPM -> the c_interface.h wrappers' outputs.
+
+The one-problem wrappers fortran_order_d_ip_ocp_hard_tv / c_order_d_ip_ocp_hard_tv take dense stage matrices from
+the host; ``OcpBatchSolver`` is their top layer for ``nprob`` problems that share stage sizes and box indices and
+whose dense data are torch tensors on the device (hpmpc_mi355x_ocp_* in include/hpmpc_mi355x.h, hk_ocp.hip).  torch is
+plumbing here (allocation, streams); packing, the solve and the outputs are HIP kernels.
+
+Dense arrays, per problem: the stage blocks concatenated in stage order,
+
+    A_k (nx[k+1] x nx[k]), B_k (nx[k+1] x nu[k]), b_k    k < N       Q_k (nx x nx), q_k                k <= N
+    S_k (nu x nx), R_k (nu x nu), r_k                     k < N       lb_k, ub_k (nb), C_k (ng x nx), lg_k, ug_k  k <= N
+    D_k (ng x nu)                                         k < N
+
+each matrix block row-major (order "C", the c_order_ convention) or column-major (order "F", fortran_order_).  The
+outputs u, x, pi have the shapes of r, q, b; lam and t are compact, [lb nb | ub nb | lg ng | ug ng] per stage.
+The host-side helpers below (numpy only, no library load) compute that layout and flatten / unflatten problems in
+the interface form of oracle/iface_oracle.py random_iface_problem.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+KEYS = ("A", "B", "b", "Q", "S", "R", "q", "r", "lb", "ub", "C", "D", "lg", "ug")  # HkOcpArray / hpmpc_mi355x_ocp_data
+OUT_KEYS = ("u", "x", "pi", "lam", "t")
+NSIZES, NOFFSETS = 29, 18  # HPMPC_MI355X_OCP_NSIZES / _NOFFSETS
+# indices into hpmpc_mi355x_ocp_sizes beyond the 14 dense arrays
+SZ = dict(BAbt=14, RSQrq=15, DCt=16, d=17, ux=18, pi=19, lam=20, ws=21, res=22, u=23, x=24, pi_out=25, lam_out=26,
+          inf_norm_res=27, N=28)
+
+
+def _shape(key, N, nx, nu, nb, ng, k):
+    """Shape of stage k's block of a dense or output array (a stage without the block has a zero dimension)."""
+    nuk = int(nu[k]) if k < N else 0
+    nxk, nbk, ngk = int(nx[k]), int(nb[k]), int(ng[k])
+    nx1 = int(nx[k + 1]) if k < N else 0
+    return {"A": (nx1, nxk), "B": (nx1, nuk), "b": (nx1,), "Q": (nxk, nxk), "S": (nuk, nxk), "R": (nuk, nuk),
+            "q": (nxk,), "r": (nuk,), "lb": (nbk,), "ub": (nbk,), "C": (ngk, nxk), "D": (ngk, nuk), "lg": (ngk,),
+            "ug": (ngk,), "u": (nuk,), "x": (nxk,), "pi": (nx1,), "lam": (2 * nbk + 2 * ngk,),
+            "t": (2 * nbk + 2 * ngk,)}[key]
+
+
+def ocp_dense_layout(N, nx, nu, nb, ng) -> dict:
+    """Doubles per problem (``sizes[key]``) and per-stage offsets (``offsets[key]``, N+1 entries) of every dense
+    array and of the outputs u, x, pi, lam, t: the formulas of hpmpc_mi355x_ocp_sizes / _offsets."""
+    sizes, offsets = {}, {}
+    for key in KEYS + OUT_KEYS:
+        off, o = np.zeros(N + 1, dtype=np.int64), 0
+        for k in range(N + 1):
+            off[k] = o
+            o += int(np.prod(_shape(key, N, nx, nu, nb, ng, k)))
+        sizes[key], offsets[key] = o, off
+    return dict(sizes=sizes, offsets=offsets)
+
+
+def _sizes_of(P):
+    return P["N"], P["nx"], P["nu"], P["nb"], P["ng"]
+
+
+def flatten_problems(problems, order="C", keys=KEYS) -> dict:
+    """Interface-form problems (same sizes) -> {key: (nprob, size) float64}: each problem's stage blocks flattened
+    in ``order`` ("C" row-major, "F" column-major) and concatenated in stage order.  Lists shorter than N+1 (A, B, b
+    with N blocks) are taken as they are."""
+    N, nx, nu, nb, ng = _sizes_of(problems[0])
+    lay = ocp_dense_layout(N, nx, nu, nb, ng)
+    out = {}
+    for key in keys:
+        arr = np.zeros((len(problems), lay["sizes"][key]))
+        for p, P in enumerate(problems):
+            if _sizes_of(P) != (N, nx, nu, nb, ng):
+                raise ValueError("the problems of a batch share their stage sizes")
+            for k, M in enumerate(P[key]):
+                M = np.asarray(M, dtype=np.float64)
+                shp = _shape(key, N, nx, nu, nb, ng, k)
+                if M.size != int(np.prod(shp)):
+                    raise ValueError(f"{key}[{k}] has {M.size} entries, expected shape {shp}")
+                o = lay["offsets"][key][k]
+                arr[p, o:o + M.size] = M.reshape(shp).flatten(order)
+        out[key] = arr
+    return out
+
+
+def unflatten_problems(flat, N, nx, nu, nb, ng, order="C", keys=None) -> list:
+    """Inverse of flatten_problems, for dense arrays and for the outputs u, x, pi, lam, t alike: {key: (nprob, size)}
+    -> one dict per problem of per-stage blocks.  A, B, b, u, pi get N blocks, the others N+1 (the interface form:
+    stage N's S, R, r, D blocks are empty)."""
+    keys = [k for k in KEYS + OUT_KEYS if k in flat] if keys is None else keys
+    lay = ocp_dense_layout(N, nx, nu, nb, ng)
+    nprob = len(np.asarray(flat[keys[0]]))
+    out = []
+    for p in range(nprob):
+        P = {}
+        for key in keys:
+            row = np.asarray(flat[key])[p]
+            nblk = N if key in ("A", "B", "b", "u", "pi") else N + 1
+            blocks = []
+            for k in range(nblk):
+                shp = _shape(key, N, nx, nu, nb, ng, k)
+                o = lay["offsets"][key][k]
+                blocks.append(row[o:o + int(np.prod(shp))].reshape(shp, order=order).copy())
+            P[key] = blocks
+        out.append(P)
+    return out
+
+
+class _OcpData(C.Structure):
+    _fields_ = [("ptr", C.c_void_p * len(KEYS)), ("stride", C.c_longlong * len(KEYS))]
+
+
+_READY = False
+
+
+def ocp_lib():
+    """The library with the argument types of the hpmpc_mi355x_ocp_* calls declared."""
+    global _READY
+    from .batch import lib
+
+    L = lib()
+    if not _READY:
+        vp, i, d = C.c_void_p, C.c_int, C.c_double
+        L.hpmpc_mi355x_ocp_plan_create.restype = vp
+        L.hpmpc_mi355x_ocp_plan_create.argtypes = [i, vp, vp, vp, vp, vp, i]
+        L.hpmpc_mi355x_ocp_plan_destroy.argtypes = [vp]
+        L.hpmpc_mi355x_ocp_tile_plan.restype = vp
+        L.hpmpc_mi355x_ocp_tile_plan.argtypes = [vp]
+        L.hpmpc_mi355x_ocp_sizes.argtypes = [vp, vp]
+        L.hpmpc_mi355x_ocp_offsets.argtypes = [vp, vp]
+        L.hpmpc_mi355x_ocp_pack_batch.restype = i
+        L.hpmpc_mi355x_ocp_pack_batch.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.hpmpc_mi355x_ocp_ipm_batch.restype = i
+        L.hpmpc_mi355x_ocp_ipm_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d, i, i, vp,
+                                                 vp, vp, vp]
+        L.hpmpc_mi355x_ocp_finish_batch.restype = i
+        L.hpmpc_mi355x_ocp_finish_batch.argtypes = [vp, i, i, i] + [vp] * 16
+        _READY = True
+    return L
+
+
+def ocp_plan_create(N, nx, nu, nb, idxb, ng, order="C"):
+    """(plan handle or None, error code, keep-alive objects) of hpmpc_mi355x_ocp_plan_create."""
+    L = ocp_lib()
+    ints = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    nuv = list(nu) + [0] * (N + 1 - len(nu))
+    arrs = [ints(nx), ints(nuv), ints(nb), ints(ng)]
+    idx = [np.ascontiguousarray(i, dtype=np.int32) for i in idxb]
+    idxp = (C.POINTER(C.c_int) * (N + 1))(*[a.ctypes.data_as(C.POINTER(C.c_int)) for a in idx])
+    plan = L.hpmpc_mi355x_ocp_plan_create(N, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data,
+                                          C.cast(idxp, C.c_void_p), arrs[3].ctypes.data, 1 if order == "C" else 0)
+    return (plan or None), L.hpmpc_mi355x_last_error(), (arrs, idx, idxp)
+
+
+class OcpBatchSolver:
+    """``nprob`` OCPs with the given stage sizes: owns the lib4 arrays, the iterate, the workspaces and the outputs
+    (torch tensors on ``device``).  pack() -> solve() -> finish(), all asynchronous on torch's current stream.
+    There is no CPU fallback: without a GPU or the built library the constructor raises."""
+
+    def __init__(self, N, nx, nu, nb, idxb, ng, nprob, order="C", device="cuda", k_max=50):
+        import torch
+
+        if order not in ("C", "F"):
+            raise ValueError("order is 'C' (row-major blocks) or 'F' (column-major blocks)")
+        if not torch.cuda.is_available():
+            raise RuntimeError("OcpBatchSolver needs a GPU (HIP device); there is no CPU fallback")
+        self.torch = torch
+        self.N, self.nprob, self.k_max, self.order = int(N), int(nprob), int(k_max), order
+        self.nx, self.nu = [int(v) for v in nx], [int(v) for v in nu][:N] + [0]
+        self.nb, self.ng = [int(v) for v in nb], [int(v) for v in ng]
+        self.dev = torch.device(device)
+        L = ocp_lib()
+        self.plan, err, self._keep = ocp_plan_create(N, self.nx, self.nu, self.nb, idxb, self.ng, order)
+        if not self.plan:
+            raise ValueError(f"unsupported problem sizes for the batched OCP front end (code {err})")
+        sz = np.zeros(NSIZES, dtype=np.int64)
+        L.hpmpc_mi355x_ocp_sizes(self.plan, sz.ctypes.data)
+        self.sizes = {k: int(sz[i]) for i, k in enumerate(KEYS)}
+        self.sizes.update({k: int(sz[i]) for k, i in SZ.items()})
+        off = np.zeros((N + 1, NOFFSETS), dtype=np.int64)
+        L.hpmpc_mi355x_ocp_offsets(self.plan, off.ctypes.data)
+        self.offsets = {k: off[:, i].copy() for i, k in enumerate(KEYS)}
+        self.offsets.update(lam_out=off[:, 14].copy(), BAbt=off[:, 15].copy(), RSQrq=off[:, 16].copy(),
+                            DCt=off[:, 17].copy())
+        P, s = self.nprob, self.sizes
+        new = lambda n, dt=torch.float64: torch.zeros((P, max(n, 1)), dtype=dt, device=self.dev)
+        self.BAbt, self.RSQrq, self.DCt, self.d = new(s["BAbt"]), new(s["RSQrq"]), new(s["DCt"]), new(s["d"])
+        self.ux, self.pi, self.lam, self.t = new(s["ux"]), new(s["pi"]), new(s["lam"]), new(s["lam"])
+        self.ws, self.res = new(s["ws"]), new(s["res"])
+        self.u, self.x, self.pi_out = new(s["u"]), new(s["x"]), new(s["pi_out"])
+        self.lam_out, self.t_out = new(s["lam_out"]), new(s["lam_out"])
+        self.inf_norm_res = new(4)
+        self.kk = torch.zeros(P, dtype=torch.int32, device=self.dev)
+        self.ret = torch.zeros(P, dtype=torch.int32, device=self.dev)
+        self.stat = new(5 * max(self.k_max, 1))
+
+    def __del__(self):
+        try:
+            if getattr(self, "plan", None):
+                ocp_lib().hpmpc_mi355x_ocp_plan_destroy(self.plan)
+        except Exception:
+            pass
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _range(self, p0, count):
+        return p0, (self.nprob - p0 if count is None else count)
+
+    def _vec(self, x, n, what):
+        """(pointer, problem stride) of a float64 device tensor: (nprob, n), or (n,) shared by every problem."""
+        torch = self.torch
+        if x.dtype != torch.float64 or x.device.type != self.dev.type:
+            raise ValueError(f"{what}: float64 tensor on {self.dev} expected")
+        if x.dim() == 1 and x.shape[0] == n and (n == 0 or x.stride(0) == 1):
+            return x.data_ptr(), 0
+        if x.dim() == 2 and tuple(x.shape) == (self.nprob, n) and (n == 0 or x.stride(1) == 1):
+            return x.data_ptr(), x.stride(0)
+        raise ValueError(f"{what}: shape ({self.nprob}, {n}) or ({n},) with unit inner stride expected, got "
+                         f"{tuple(x.shape)}")
+
+    def data_struct(self, data):
+        ds = _OcpData()
+        for i, key in enumerate(KEYS):
+            n = self.sizes[key]
+            if n == 0 and data.get(key) is None:
+                ds.ptr[i], ds.stride[i] = None, 0
+                continue
+            if data.get(key) is None:
+                raise ValueError(f"dense array {key} missing")
+            ds.ptr[i], ds.stride[i] = self._vec(data[key], n, key)
+        return ds
+
+    def pack(self, data, matrices=True, warm=None, p0=0, count=None):
+        """Dense device tensors -> BAbt, RSQrq, DCt, d (hk_ocp_pack).  ``data``: {key: tensor (nprob, size), or
+        (size,) for an array shared by every problem (stride 0)}.  matrices=False rewrites only b, q, r and the
+        bounds.  warm: {"u": (nprob, sizes["u"]), "x": (nprob, sizes["x"])} packed into ux for warm_start=1."""
+        p0, count = self._range(p0, count)
+        ds = self.data_struct(data)
+        u0 = x0 = ux = None
+        if warm is not None:
+            u0, su = self._vec(warm["u"], self.sizes["u"], "warm u")
+            x0, sx = self._vec(warm["x"], self.sizes["x"], "warm x")
+            if (su, sx) != (self.sizes["u"], self.sizes["x"]) and self.nprob > 1:
+                raise ValueError("warm u / x: contiguous (nprob, size) tensors expected")
+            ux = self.ux.data_ptr()
+        rc = ocp_lib().hpmpc_mi355x_ocp_pack_batch(
+            self.plan, C.byref(ds), 1 if matrices else 0, self.nprob, p0, count, self.BAbt.data_ptr(),
+            self.RSQrq.data_ptr(), self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), u0, x0, ux,
+            self._stream())
+        if rc != 0:
+            raise RuntimeError(f"hpmpc_mi355x_ocp_pack_batch failed ({rc})")
+
+    def solve(self, mu0=2.0, mu_tol=1e-10, alpha_min=1e-8, warm_start=0, p0=0, count=None):
+        """d_ip2_res_mpc_hard_tv on the packed batch (mu0 > 0: one value for the batch)."""
+        p0, count = self._range(p0, count)
+        rc = ocp_lib().hpmpc_mi355x_ocp_ipm_batch(
+            self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
+            self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
+            self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(), self.k_max, mu0, mu_tol,
+            alpha_min, warm_start, 1, self.kk.data_ptr(), self.ret.data_ptr(), self.stat.data_ptr(), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"hpmpc_mi355x_ocp_ipm_batch failed ({rc})")
+
+    def finish(self, p0=0, count=None) -> dict:
+        """The wrappers' outputs as device tensors (nprob, size): u, x (equality-box fix applied), pi, compact lam
+        and t, inf_norm_res (nprob, 4), kk and status per problem.  Asynchronous: synchronise before reading."""
+        p0, count = self._range(p0, count)
+        rc = ocp_lib().hpmpc_mi355x_ocp_finish_batch(
+            self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
+            self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
+            self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.res.data_ptr(), self.u.data_ptr(),
+            self.x.data_ptr(), self.pi_out.data_ptr(), self.lam_out.data_ptr(), self.t_out.data_ptr(),
+            self.inf_norm_res.data_ptr(), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"hpmpc_mi355x_ocp_finish_batch failed ({rc})")
+        s = self.sizes
+        return dict(u=self.u[:, :s["u"]], x=self.x[:, :s["x"]], pi=self.pi_out[:, :s["pi_out"]],
+                    lam=self.lam_out[:, :s["lam_out"]], t=self.t_out[:, :s["lam_out"]],
+                    inf_norm_res=self.inf_norm_res, kk=self.kk, status=self.ret)
+
+    def results(self, out=None) -> list:
+        """finish()'s tensors on the host, one interface-form dict per problem (synchronises)."""
+        out = self.finish() if out is None else out
+        self.torch.cuda.synchronize(self.dev)
+        host = {k: v.cpu().numpy() for k, v in out.items()}
+        per = unflatten_problems(host, self.N, self.nx, self.nu, self.nb, self.ng, self.order, keys=OUT_KEYS)
+        for p, r in enumerate(per):
+            r.update(inf_norm_res=host["inf_norm_res"][p].copy(), kk=int(host["kk"][p]), status=int(host["status"][p]),
+                     stat=self.stat[p, :5 * max(int(host["kk"][p]), 0)].cpu().numpy())
+        return per

@@ -471,6 +471,95 @@ int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan *plan, const hpmpc_
                                 double *ws, int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
                                 int compute_mult, int *kk, int *ret, double *stat, void *stream);
 
+/* ---- the OCP front end for device-resident batches ----
+ * The top layer of the include/c_interface.h wrappers (fortran_order_d_ip_ocp_hard_tv / c_order_d_ip_ocp_hard_tv)
+ * for a batch of problems that share stage sizes and box indices and whose DENSE data are already in HBM: pack to
+ * lib4 on the device, solve, and unpack to the wrappers' outputs, with no host copy in between.
+ *   hpmpc_mi355x_ocp_pack_batch   dense A, B, b, Q, S, R, q, r, lb, ub, C, D, lg, ug -> BAbt, RSQrq, DCt, d (ux)
+ *   hpmpc_mi355x_ocp_ipm_batch    d_ip2_res_mpc_hard_tv on the packed arrays, general constraints included
+ *   hpmpc_mi355x_ocp_finish_batch u, x (with the equality-box fix), pi, compact lam / t, inf_norm_res
+ * Tile-path sizes only (see the top of this file), and the full space only: there is no N2; partially condensed
+ * batches go through the hpmpc_mi355x_pcond_* pipeline.  Every other Part-2 call (hpmpc_mi355x_ipm_batch, _solo,
+ * _pass, _queue, the ric_*_batch calls) still refuses a plan with ng > 0: they carry no DCt array.
+ *
+ * Dense arrays (device pointers, doubles).  Inside one problem the stage blocks are concatenated in stage order:
+ *   A_k (nx[k+1] x nx[k]), B_k (nx[k+1] x nu[k]), b_k (nx[k+1])        k < N
+ *   Q_k (nx[k] x nx[k]), q_k (nx[k])                                   k <= N
+ *   S_k (nu[k] x nx[k]), R_k (nu[k] x nu[k]), r_k (nu[k])              k < N
+ *   lb_k, ub_k (nb[k]); C_k (ng[k] x nx[k]), lg_k, ug_k (ng[k])        k <= N;     D_k (ng[k] x nu[k])  k < N
+ * each matrix block column-major (row_major = 0, the fortran_order_ convention) or row-major (row_major = 1, the
+ * c_order_ convention).  Every array has its own problem stride; stride 0 means one copy shared by every problem
+ * (time-invariant data).  An array whose per-problem size is 0 (C, D, lg, ug without general constraints; lb, ub
+ * without boxes) may be null.
+ * Packed arrays: problem-major, per-problem sizes from hpmpc_mi355x_ocp_sizes, in the tile plan's packed default
+ * layout (BAbt_k / RSQrq_k / DCt_k at the offsets hpmpc_mi355x_ocp_offsets reports; d, lam, t 32 doubles per stage
+ * as [lb pnb | ub pnb | lg png | ug png]; ux, pi 16 doubles per stage) -- with ng = 0 they can be handed, with
+ * hpmpc_mi355x_ocp_tile_plan's plan and a null layout, to hpmpc_mi355x_ipm_batch / _solo / _queue.
+ * Outputs: u, x, pi shaped like r, q, b; lam, t per stage compact as [lb nb | ub nb | lg ng | ug ng], stages
+ * concatenated; inf_norm_res 4 doubles per problem = max|r_q|, max|r_b|, max|r_d|, mu of d_res_mpc_hard_tv, over
+ * the elements the one-problem wrappers visit.
+ * All calls are asynchronous on `stream` (a hipStream_t, or null) and synchronise with nothing (plan creation
+ * uploads its tables once); only problems [p0, p0+count) are read or written; count = 0 returns 0 and does
+ * nothing; a null required pointer, a bad range or a refused launch returns HPMPC_MI355X_EUNSUPPORTED. */
+typedef struct hpmpc_mi355x_ocp_plan hpmpc_mi355x_ocp_plan;
+/* index of each dense array in hpmpc_mi355x_ocp_data, hpmpc_mi355x_ocp_sizes and hpmpc_mi355x_ocp_offsets */
+enum {
+    HPMPC_MI355X_OCP_A, HPMPC_MI355X_OCP_B, HPMPC_MI355X_OCP_b, HPMPC_MI355X_OCP_Q, HPMPC_MI355X_OCP_S,
+    HPMPC_MI355X_OCP_R, HPMPC_MI355X_OCP_q, HPMPC_MI355X_OCP_r, HPMPC_MI355X_OCP_lb, HPMPC_MI355X_OCP_ub,
+    HPMPC_MI355X_OCP_C, HPMPC_MI355X_OCP_D, HPMPC_MI355X_OCP_lg, HPMPC_MI355X_OCP_ug, HPMPC_MI355X_OCP_NARRAYS
+};
+typedef struct {
+    const double *ptr[HPMPC_MI355X_OCP_NARRAYS];  /* device pointers: A, B, b, Q, S, R, q, r, lb, ub, C, D, lg, ug */
+    long long stride[HPMPC_MI355X_OCP_NARRAYS];   /* doubles between problems (0: shared by all problems) */
+} hpmpc_mi355x_ocp_data;
+/* nu has N+1 entries (nu[N] is treated as 0); idxb[k] lists the nb[k] boxed variables of stage k.  NULL with
+ * hpmpc_mi355x_last_error() = HPMPC_MI355X_EUNSUPPORTED where hpmpc_mi355x_plan_create refuses, and for
+ * nb[k] > nu[k] + nx[k]. */
+hpmpc_mi355x_ocp_plan *hpmpc_mi355x_ocp_plan_create(int N, const int *nx, const int *nu, const int *nb,
+                                                    const int *const *idxb, const int *ng, int row_major);
+void hpmpc_mi355x_ocp_plan_destroy(hpmpc_mi355x_ocp_plan *plan);
+/* the tile plan the packed arrays belong to (owned by the OCP plan) */
+const hpmpc_mi355x_plan *hpmpc_mi355x_ocp_tile_plan(const hpmpc_mi355x_ocp_plan *plan);
+/* out[HPMPC_MI355X_OCP_NSIZES], doubles per problem: [0..13] the dense arrays (order above) | [14] BAbt, [15] RSQrq,
+ * [16] DCt, [17] d, [18] ux, [19] pi, [20] lam (= t), [21] ws, [22] the residual scratch of
+ * hpmpc_mi355x_ocp_finish_batch | outputs [23] u (= u0), [24] x (= x0), [25] pi, [26] lam (= t), [27] inf_norm_res |
+ * [28] N */
+#define HPMPC_MI355X_OCP_NSIZES 29
+int hpmpc_mi355x_ocp_sizes(const hpmpc_mi355x_ocp_plan *plan, long long *out);
+/* out[HPMPC_MI355X_OCP_NOFFSETS * (N+1)], per stage: [0..13] the stage's block inside one problem of each dense
+ * array (the u / x / pi outputs sit at the offsets of r / q / b), [14] its lam / t output, [15] BAbt_k, [16] RSQrq_k,
+ * [17] DCt_k inside the packed arrays */
+#define HPMPC_MI355X_OCP_NOFFSETS 18
+int hpmpc_mi355x_ocp_offsets(const hpmpc_mi355x_ocp_plan *plan, long long *out);
+/* Dense -> packed, exactly the elements oracle/iface_oracle.py to_qp builds (the one-problem wrappers' packing,
+ * with S in both triangles of RSQrq_k).  matrices != 0 writes EVERY element of BAbt, RSQrq, DCt and d of the
+ * problems in range, padding as zeros: the buffers need no initialisation.  matrices = 0 rewrites only the b row of
+ * BAbt_k, the r / q row of RSQrq_k and d (the KKT wrappers' re-pack; the per-step update of a receding-horizon
+ * loop) and leaves every other element as it was.  u0, x0, ux: all three given, ux_k = [u0_k | x0_k | 0..] is
+ * written for warm_start = 1 (u0 / x0 shaped like the u / x outputs); else ux is not touched.  DCt may be null when
+ * every ng is 0. */
+int hpmpc_mi355x_ocp_pack_batch(const hpmpc_mi355x_ocp_plan *plan, const hpmpc_mi355x_ocp_data *data, int matrices,
+                                int nprob, int p0, int count, double *BAbt, double *RSQrq, double *DCt, double *d,
+                                const double *u0, const double *x0, double *ux, void *stream);
+/* hpmpc_mi355x_ipm_batch (the same pass kernels: init, then k_max x (factorisation, predictor, corrector, update))
+ * on the packed default layout, plus DCt (null when every ng is 0).  kk, ret per problem, stat 5*k_max per problem;
+ * ws: hpmpc_mi355x_ocp_sizes()[21] doubles per problem (= hpmpc_mi355x_ws_doubles of the tile plan).  mu0 must be > 0
+ * (HPMPC_MI355X_EUNSUPPORTED otherwise): the one-problem wrappers replace mu0 <= 0 by the problem's largest cost
+ * entry, a per-problem value, and the batched kernels take one mu0 for the whole batch. */
+int hpmpc_mi355x_ocp_ipm_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, int p0, int count, const double *BAbt,
+                               const double *RSQrq, const double *DCt, const double *d, double *ux, double *pi,
+                               double *lam, double *t, double *ws, int k_max, double mu0, double mu_tol,
+                               double alpha_min, int warm_start, int compute_mult, int *kk, int *ret, double *stat,
+                               void *stream);
+/* The wrappers' outputs from the iterate: the plain residuals d_res_mpc_hard_tv over the batch into `res` (nprob *
+ * hpmpc_mi355x_ocp_sizes()[22] doubles, no initialisation needed; ws and its factor are not touched), then u, x,
+ * pi_out, lam_out, inf_norm_res and, when t_out is not null, t_out. */
+int hpmpc_mi355x_ocp_finish_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, int p0, int count, const double *BAbt,
+                                  const double *RSQrq, const double *DCt, const double *d, const double *ux,
+                                  const double *pi, const double *lam, const double *t, double *res, double *u,
+                                  double *x, double *pi_out, double *lam_out, double *t_out, double *inf_norm_res,
+                                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif
