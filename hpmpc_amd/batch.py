@@ -146,6 +146,58 @@ def unpack_batch(template: OCPQP, hB, hR, hd) -> OCPQP:
                  [i.copy() for i in template.idxb], BAbt, RSQrq, d, [], hB.shape[0])
 
 
+def kkt_scratch_doubles(N: int) -> int:
+    """Doubles of scratch one right-hand-side set of the batched KKT re-solve needs: six 16-double and four
+    32-double vectors per stage (KKT_SCRATCH_V16 / _V32 of csrc/hk_kkt_args.h; hpmpc_mi355x_kkt_scratch_doubles)."""
+    return (N + 1) * (6 * 16 + 4 * 32)
+
+
+_KKT_READY = False
+
+
+def kkt_lib() -> C.CDLL:
+    """The library with the argument types of the batched KKT re-solve declared (on first use, not in lib(): an
+    A/B library from before these calls, HPMPC_MI355X_LIB, still loads for everything else)."""
+    global _KKT_READY
+    L = lib()
+    if not _KKT_READY:
+        vp, i = C.c_void_p, C.c_int
+        L.hpmpc_mi355x_kkt_scratch_doubles.restype = C.c_longlong
+        L.hpmpc_mi355x_kkt_scratch_doubles.argtypes = [vp]
+        L.hpmpc_mi355x_kkt_new_rhs_batch.restype = i
+        L.hpmpc_mi355x_kkt_new_rhs_batch.argtypes = [vp, vp, i, i, i, i] + [vp] * 12 + [i, vp]
+        _KKT_READY = True
+    return L
+
+
+def kkt_buffers(torch, dev, plan, N: int, nprob: int, nrhs: int) -> dict:
+    """Outputs and scratch of hpmpc_mi355x_kkt_new_rhs_batch for ``nrhs`` sets per problem: ux, pi (nprob, nrhs, N+1,
+    16), lam, t (nprob, nrhs, N+1, 32), scratch (nprob, nrhs, hpmpc_mi355x_kkt_scratch_doubles)."""
+    f64 = torch.float64
+    new = lambda *shape: torch.zeros((nprob, nrhs) + shape, dtype=f64, device=dev)
+    return dict(ux=new(N + 1, 16), pi=new(N + 1, 16), lam=new(N + 1, 32), t=new(N + 1, 32),
+                scratch=new(int(kkt_lib().hpmpc_mi355x_kkt_scratch_doubles(plan))))
+
+
+def kkt_sets_call(torch, plan, layout, N, nprob, p0, count, nrhs, BAbt, RSQrq, DCt, b, q, d, out, ws, compute_mult,
+                  stream) -> int:
+    """hpmpc_mi355x_kkt_new_rhs_batch on torch tensors, after checking the shapes of the per-set arrays: b, q (nprob,
+    nrhs, N+1, 16) or None (the problem's augmented rows), d (nprob, nrhs, N+1, 32), ``out`` from kkt_buffers.
+    Returns the library's code."""
+    for name, x, w in (("b", b, 16), ("q", q, 16), ("d", d, 32)):
+        if x is None and name != "d":
+            continue
+        if x is None or tuple(x.shape) != (nprob, nrhs, N + 1, w) or x.dtype != torch.float64 or not x.is_contiguous():
+            raise ValueError(f"{name}: contiguous float64 tensor of shape {(nprob, nrhs, N + 1, w)} expected")
+    for name, w in (("ux", 16), ("pi", 16), ("lam", 32), ("t", 32)):
+        if tuple(out[name].shape) != (nprob, nrhs, N + 1, w):
+            raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={nrhs}) expected")
+    ptr = lambda x: None if x is None else x.data_ptr()
+    return kkt_lib().hpmpc_mi355x_kkt_new_rhs_batch(
+        plan, layout, nprob, p0, count, nrhs, ptr(BAbt), ptr(RSQrq), ptr(DCt), ptr(b), ptr(q), ptr(d), ptr(out["ux"]),
+        ptr(out["pi"]), ptr(out["lam"]), ptr(out["t"]), ptr(ws), ptr(out["scratch"]), compute_mult, stream)
+
+
 class BatchSolver:
     """Device-resident batch of OCP QPs + the batched HPMPC entry points.
 
@@ -250,6 +302,30 @@ class BatchSolver:
             self.ret.data_ptr(), self.stat.data_ptr(), self._stream())
         if rc != 0:
             raise RuntimeError(f"hpmpc_mi355x_ipm_solo failed ({rc})")
+
+    def kkt_buffers(self, nrhs: int = 1) -> dict:
+        """The output and scratch tensors kkt_new_rhs(nrhs=nrhs) writes (allocated on first use, then reused)."""
+        if nrhs < 1:
+            raise ValueError("nrhs >= 1 expected")
+        bufs = self.__dict__.setdefault("_kkt", {})
+        if nrhs not in bufs:
+            bufs[nrhs] = kkt_buffers(self.torch, self.dev, self.plan, self.N, self.nprob, nrhs)
+        return bufs[nrhs]
+
+    def kkt_new_rhs(self, b, q, d, nrhs=1, p0=0, count=None, compute_mult=1):
+        """Batched d_kkt_solve_new_rhs_res_mpc_hard_tv on the factor ipm() / ipm_solo() left in ws (at least one
+        iteration done; not after a queue solve): ``nrhs`` right-hand-side sets per problem in one launch.  b, q:
+        (nprob, nrhs, N+1, 16) device tensors (b in state order, q in variable order [r | q]) or None for the
+        problem's own rows; d: (nprob, nrhs, N+1, 32).  Returns ux, pi, lam, t with a leading (nprob, nrhs) shape --
+        the tensors of kkt_buffers(nrhs), overwritten by the next call.  ws and the problem data are not written.
+        Asynchronous on torch's current stream."""
+        count = self.nprob - p0 if count is None else count
+        out = self.kkt_buffers(nrhs)
+        rc = kkt_sets_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, nrhs, self.BAbt,
+                           self.RSQrq, None, b, q, d, out, self.ws, compute_mult, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"hpmpc_mi355x_kkt_new_rhs_batch failed ({rc})")
+        return out["ux"], out["pi"], out["lam"], out["t"]
 
     def ipm_pass(self, pss, *, mu0=2.0, mu_tol=1e-12, alpha_min=1e-8, warm_start=0, compute_mult=1, p0=0,
                  count=None):

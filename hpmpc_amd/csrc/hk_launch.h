@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 struct KArgs;
+struct KktArgs;
 struct SoftArgs;
 struct SoftResArgs;
 struct WideIpmArgs;
@@ -25,6 +26,8 @@ int hk_soft_launch(int which, const SoftArgs* a, int count, hipStream_t stream);
 int hk_soft_res_launch(const SoftResArgs* a, hipStream_t stream);
 // hk_soft_ipm.hip: the batched soft-constraint IPM, init launch + one launch for every iteration of every problem
 int hk_soft_ipm_launch(const KArgs* a, const SoftArgs* s, int count, hipStream_t stream);
+// hk_kkt.hip: the batched KKT re-solve, x->nrhs right-hand-side sets for each of `count` problems in one launch
+int hk_kkt_rhs_launch(const KArgs* a, const KktArgs* x, int count, hipStream_t stream);
 // hk_wide.hip (which: HkWideLaunch; args: the WideArgs / PcArgs / PxArgs of that kernel) and hk_wide_ipm.hip
 int hk_wide_launch(int which, const void* args, int count, int lds_doubles, hipStream_t stream);
 int hk_wide_ipm_launch(const WideIpmArgs* a, int count, int lds_doubles, hipStream_t stream);

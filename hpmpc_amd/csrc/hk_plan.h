@@ -1,8 +1,8 @@
 // hk_plan.h -- the tile path's plan and the one-problem staging carve, shared by the host files of that path:
 // hpmpc_capi.cpp (plan, layout tables, batched API; defines the plan functions below), hpmpc_capi_queue.cpp (the
 // problem queue), hpmpc_capi_dropin.cpp (reference-named hard-constraint entry points; defines the arena functions)
-// hpmpc_capi_soft.cpp (soft-constraint IPM and residual; defines the soft refusals and layout) and
-// hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM).
+// hpmpc_capi_soft.cpp (soft-constraint IPM and residual; defines the soft refusals and layout),
+// hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM) and hpmpc_capi_kkt.cpp (the batched KKT re-solve).
 #pragma once
 #include <mutex>
 #include <vector>
@@ -55,6 +55,8 @@ bool plan_supported(int N, const int* nx, const int* nu, const int* nb, const in
                     const char** why);
 KArgs base_args(const hpmpc_mi355x_plan* P, int nprob, int p0);
 bool layout_apply(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a);
+// layout_apply without its ng > 0 refusal, for the calls that carry a DCt array (hpmpc_capi_kkt.cpp)
+bool layout_set(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a);
 int launch(int which, const KArgs* a, int count, hipStream_t s);  // hk_launch, or the ric2 variant's two-wave sv
 // the IPM fields of `a` (plan tables and layout already set) and the launch `which`: shared by every batched IPM call
 int ipm_run(KArgs& a, int count, const double* BAbt, const double* RSQrq, const double* d, double* ux, double* pi,

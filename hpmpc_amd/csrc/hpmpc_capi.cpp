@@ -254,6 +254,10 @@ bool layout_apply(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a
                                            "reference-named entry points");
         return false;
     }
+    return layout_set(P, lay, a);
+}
+
+bool layout_set(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a) {
     if (lay && lay->BAbt_off && lay->RSQrq_off) {
         a.st = plan_stage_table(P, lay->BAbt_off, lay->RSQrq_off, lay->BAbt_shared, lay->RSQrq_shared);
         if (!a.st) return false;

@@ -6,6 +6,7 @@
 // All IPM control flow (iteration count, step length, mu) is per wave, so problems that converge
 // early simply retire their wave.
 #include "hk_ipm_body.h"
+#include "hk_kkt_body.h"
 #include "hk_launch.h"
 #include "hk_mw.h"
 #include <cstdlib>
@@ -504,85 +505,14 @@ __global__ __launch_bounds__(64) void hk_kkt_new_rhs(KArgs a) {
     RicIO io = make_io(a, T, p, w.F);
     BoxTab bt{T.tileslot, T.slotvar};
     const long o16 = (long)p * a.sV16, o32 = (long)p * a.sV32;
+    // the body (hk_kkt_body.h) with every work vector in the problem's own workspace
     double* ux = a.ux + o16;
     double* pi = a.pi + o16;
     double* lam = a.lam + o32;
     double* t = a.t + o32;
     const double* dv = a.d + o32;
-    const int l = lane_id();
-    BoxCtx bc = box_ctx(w, dv, lam, t);
-    for (int i = l; i < (N + 1) * V16; i += 64) {
-        ux[i] = w.ux_bkp[i];
-        pi[i] = w.pi_bkp[i];
-    }
-    for (int i = l; i < (N + 1) * V32; i += 64) {
-        t[i] = w.t_bkp[i];
-        lam[i] = w.lam_bkp[i];
-    }
-    wsync();
-    double mu = 0.0;
-    ResIO ro{};
-    ro.bsrc = a.vb + o16;
-    ro.qsrc = a.vq + o16;
-    ro.ux = ux;
-    ro.pi = pi;
-    ro.rq = w.res_q;
-    ro.rb = w.res_b;
-    ro.rd = w.res_d;
-    ro.rm = w.res_m;
-    residual_pass<false, FX>(io, bc, ro, mu);
-    wsync();
-    HK_FOR_BOX(io, k, {
-        w.qx[k * V16 + slot] = w.t_inv[lo] * (w.res_m[lo] - lam[lo] * w.res_d[lo]) -
-                               w.t_inv[up] * (w.res_m[up] + lam[up] * w.res_d[up]);
-    });
-    HK_FOR_GEN(io, k, {
-        w.qx[s16] = w.t_inv[lo] * (w.res_m[lo] - lam[lo] * w.res_d[lo]) -
-                    w.t_inv[up] * (w.res_m[up] + lam[up] * w.res_d[up]);
-    });
-    wsync();
-    double al = 1.0;
-    ric_trs<BX_GIVEN, BX_NONE, FX>(io, &sm, w.res_b, w.res_q, bc, w.dux, a.compute_mult, w.dpi, 1, w.Pb, al);
-    wsync();
-    HK_FOR_BOX(io, k, {  // d_compute_dt_dlam_res + d_update_var_res (alpha = 1)
-        const int v = bt.slotvar[k * 16 + slot];
-        const double x = w.dux[k * V16 + v];
-        const double dtl = x - w.res_d[lo], dtu = -x + w.res_d[up];
-        const double dll = -w.t_inv[lo] * (lam[lo] * dtl + w.res_m[lo]);
-        const double dlu = -w.t_inv[up] * (lam[up] * dtu + w.res_m[up]);
-        w.dt[lo] = dtl;
-        w.dt[up] = dtu;
-        w.dlam[lo] = dll;
-        w.dlam[up] = dlu;
-    });
-    if (a.ngt) {  // the general slots: the same update from D dux (gen_alpha's phase-2 branch)
-        for (int k = 0; k <= N; k++) {
-            const StageInfo si = load_stage(io.st, k);
-            if (si.ng == 0) continue;
-            const DynSh sh(si);
-            const int vc = tile_var(l & 15, sh.nu, sh.nx, sh.xo);
-            double dummy = 1.0;
-            gen_alpha<BX_P2>(io, sh, k, bc, gld(w.dux, k * V16 + vc, vc >= 0), dummy);
-        }
-    }
-    wsync();
-    for (int k = 0; k <= N; k++) {
-        const StageInfo si = load_stage(io.st, k);
-        if (l < si.nu + si.nx) ux[k * V16 + l] += 1.0 * w.dux[k * V16 + l];
-        if (k < N && l < si.nx1) pi[k * V16 + l] += 1.0 * w.dpi[k * V16 + l];
-    }
-    HK_FOR_BOX(io, k, {
-        lam[lo] += 1.0 * w.dlam[lo];
-        lam[up] += 1.0 * w.dlam[up];
-        t[lo] += 1.0 * w.dt[lo];
-        t[up] += 1.0 * w.dt[up];
-    });
-    HK_FOR_GEN(io, k, {
-        lam[lo] += 1.0 * w.dlam[lo];
-        lam[up] += 1.0 * w.dlam[up];
-        t[lo] += 1.0 * w.dt[lo];
-        t[up] += 1.0 * w.dt[up];
-    });
+    const KktIO v{a.vb, a.vq, o16, dv, ux, pi, lam, t};
+    kkt_body<FX, false>(a, io, &sm, bt, w, v);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -104,6 +104,33 @@ def unflatten_problems(flat, N, nx, nu, nb, ng, order="C", keys=None) -> list:
     return out
 
 
+def kkt_set_arrays(problems):
+    """The per-set arrays of the batched KKT re-solve from interface-form problems (one set each, same sizes):
+    b (n, N+1, 16) with b_k in state order, q (n, N+1, 16) in variable order [r_k | q_k], d (n, N+1, 32) as
+    [lb pnb | ub pnb | lg png | ug png], padding zero -- the vectors hpmpc_amd.cabi.bq_from_qp extracts from the
+    packed problem and the d of oracle/iface_oracle.py to_qp, element for element.  For ``nrhs`` sets per problem
+    order the sets problem-major and reshape to (nprob, nrhs, N+1, .)."""
+    N, nx, nu, nb, ng = _sizes_of(problems[0])
+    n = len(problems)
+    b, q, d = np.zeros((n, N + 1, 16)), np.zeros((n, N + 1, 16)), np.zeros((n, N + 1, 32))
+    for p, P in enumerate(problems):
+        if _sizes_of(P) != (N, nx, nu, nb, ng):
+            raise ValueError("the problems of a batch share their stage sizes")
+        for k in range(N + 1):
+            nuk = int(nu[k]) if k < N else 0
+            nxk, nbk, ngk = int(nx[k]), int(nb[k]), int(ng[k])
+            pnb, png = (nbk + 3) // 4 * 4, (ngk + 3) // 4 * 4
+            if k < N:
+                b[p, k, :int(nx[k + 1])] = P["b"][k]
+                q[p, k, :nuk] = P["r"][k]
+            q[p, k, nuk:nuk + nxk] = P["q"][k]
+            d[p, k, :nbk] = P["lb"][k]
+            d[p, k, pnb:pnb + nbk] = P["ub"][k]
+            d[p, k, 2 * pnb:2 * pnb + ngk] = P["lg"][k]
+            d[p, k, 2 * pnb + png:2 * pnb + png + ngk] = P["ug"][k]
+    return b, q, d
+
+
 class _OcpData(C.Structure):
     _fields_ = [("ptr", C.c_void_p * len(KEYS)), ("stride", C.c_longlong * len(KEYS))]
 
@@ -133,6 +160,9 @@ def ocp_lib():
                                                  vp, vp, vp]
         L.hpmpc_mi355x_ocp_finish_batch.restype = i
         L.hpmpc_mi355x_ocp_finish_batch.argtypes = [vp, i, i, i] + [vp] * 16
+        if hasattr(L, "hpmpc_mi355x_ocp_kkt_batch"):  # absent from an A/B library of before it (HPMPC_MI355X_LIB)
+            L.hpmpc_mi355x_ocp_kkt_batch.restype = i
+            L.hpmpc_mi355x_ocp_kkt_batch.argtypes = [vp, i, i, i] + [vp] * 11
         _READY = True
     return L
 
@@ -152,7 +182,8 @@ def ocp_plan_create(N, nx, nu, nb, idxb, ng, order="C"):
 
 class OcpBatchSolver:
     """``nprob`` OCPs with the given stage sizes: owns the lib4 arrays, the iterate, the workspaces and the outputs
-    (torch tensors on ``device``).  pack() -> solve() -> finish(), all asynchronous on torch's current stream.
+    (torch tensors on ``device``).  pack() -> solve() -> finish(), then any number of resolve() -> finish() or
+    kkt_sets() on the factor solve() left, all asynchronous on torch's current stream.
     There is no CPU fallback: without a GPU or the built library the constructor raises."""
 
     def __init__(self, N, nx, nu, nb, idxb, ng, nprob, order="C", device="cuda", k_max=50):
@@ -259,6 +290,52 @@ class OcpBatchSolver:
             alpha_min, warm_start, 1, self.kk.data_ptr(), self.ret.data_ptr(), self.stat.data_ptr(), self._stream())
         if rc != 0:
             raise RuntimeError(f"hpmpc_mi355x_ocp_ipm_batch failed ({rc})")
+
+    def kkt_buffers(self, nrhs: int = 1) -> dict:
+        """The output and scratch tensors kkt_sets(nrhs=nrhs) writes (allocated on first use, then reused);
+        resolve() uses the scratch of nrhs = 1."""
+        from .batch import kkt_buffers
+
+        if nrhs < 1:
+            raise ValueError("nrhs >= 1 expected")
+        bufs = self.__dict__.setdefault("_kkt", {})
+        if nrhs not in bufs:
+            bufs[nrhs] = kkt_buffers(self.torch, self.dev, ocp_lib().hpmpc_mi355x_ocp_tile_plan(self.plan), self.N,
+                                     self.nprob, nrhs)
+        return bufs[nrhs]
+
+    def resolve(self, data, p0=0, count=None):
+        """The batched c_order_ / fortran_order_d_solve_kkt_new_rhs_ocp_hard_tv: re-solve the last Newton system of
+        solve() for the b, q, r and bounds of ``data`` (dense tensors as for pack(); its matrices are not read).
+        The vectors-only pack, then hpmpc_mi355x_ocp_kkt_batch into the solver's own iterate (ux, pi, lam, t);
+        finish() then gives the wrapper's outputs (its kk / status are still solve()'s).  ws keeps the factor, so
+        resolve() may be called again with other data.  Needs a solve() with at least one iteration."""
+        p0, count = self._range(p0, count)
+        self.pack(data, matrices=False, p0=p0, count=count)
+        rc = ocp_lib().hpmpc_mi355x_ocp_kkt_batch(
+            self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
+            self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
+            self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(),
+            self.kkt_buffers(1)["scratch"].data_ptr(), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"hpmpc_mi355x_ocp_kkt_batch failed ({rc})")
+
+    def kkt_sets(self, b, q, d, nrhs=1, p0=0, count=None, compute_mult=1):
+        """hpmpc_mi355x_kkt_new_rhs_batch with the tile plan on the packed arrays: ``nrhs`` right-hand-side sets per
+        problem against the factor of solve().  b, q: (nprob, nrhs, N+1, 16) device tensors or None (the rows
+        packed into BAbt / RSQrq); d: (nprob, nrhs, N+1, 32) (kkt_set_arrays builds all three).  Returns ux, pi,
+        lam, t with a leading (nprob, nrhs) shape in the padded layouts of the iterate -- the tensors of
+        kkt_buffers(nrhs).  Neither ws nor the solver's iterate is written."""
+        from .batch import kkt_sets_call
+
+        p0, count = self._range(p0, count)
+        out = self.kkt_buffers(nrhs)
+        rc = kkt_sets_call(self.torch, ocp_lib().hpmpc_mi355x_ocp_tile_plan(self.plan), None, self.N, self.nprob, p0,
+                           count, nrhs, self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None, b, q, d, out,
+                           self.ws, compute_mult, self._stream())
+        if rc != 0:
+            raise RuntimeError(f"hpmpc_mi355x_kkt_new_rhs_batch failed ({rc})")
+        return out["ux"], out["pi"], out["lam"], out["t"]
 
     def finish(self, p0=0, count=None) -> dict:
         """The wrappers' outputs as device tensors (nprob, size): u, x (equality-box fix applied), pi, compact lam

@@ -480,7 +480,8 @@ int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan *plan, const hpmpc_
  *   hpmpc_mi355x_ocp_finish_batch u, x (with the equality-box fix), pi, compact lam / t, inf_norm_res
  * Tile-path sizes only (see the top of this file), and the full space only: there is no N2; partially condensed
  * batches go through the hpmpc_mi355x_pcond_* pipeline.  Every other Part-2 call (hpmpc_mi355x_ipm_batch, _solo,
- * _pass, _queue, the ric_*_batch calls) still refuses a plan with ng > 0: they carry no DCt array.
+ * _pass, _queue, the ric_*_batch calls) still refuses a plan with ng > 0: they carry no DCt array
+ * (hpmpc_mi355x_kkt_new_rhs_batch below does, and takes such a plan).
  *
  * Dense arrays (device pointers, doubles).  Inside one problem the stage blocks are concatenated in stage order:
  *   A_k (nx[k+1] x nx[k]), B_k (nx[k+1] x nu[k]), b_k (nx[k+1])        k < N
@@ -559,6 +560,44 @@ int hpmpc_mi355x_ocp_finish_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, 
                                   const double *pi, const double *lam, const double *t, double *res, double *u,
                                   double *x, double *pi_out, double *lam_out, double *t_out, double *inf_norm_res,
                                   void *stream);
+
+/* ---- the KKT re-solve for device-resident batches, many right-hand sides per factor ----
+ * d_kkt_solve_new_rhs_res_mpc_hard_tv (include/mpc_solvers.h:46, mpc_solvers/d_ip2_res_hard.c:1922) on a batch: the
+ * last Newton system of an IPM re-solved for new b, q / r and bounds, one Riccati solve on the persisted factor per
+ * right-hand-side set instead of a whole IPM solve (the feedback step of a real-time iteration, a scenario fan-out
+ * over one linearisation).  Every problem takes nrhs sets; set s = p * nrhs + r belongs to problem p.  One launch,
+ * one wavefront per set; the sets of a problem share its matrices and workspace, both read only.
+ * Which ws is valid: the workspaces hpmpc_mi355x_ipm_batch, hpmpc_mi355x_ipm_solo or hpmpc_mi355x_ocp_ipm_batch left
+ * for the same problems (same plan, same BAbt / RSQrq / DCt matrices), with at least one iteration done (kk >= 1).
+ * After kk = 0 the workspace holds no factor and the result is undefined, as in the reference.  A queue solve
+ * (hpmpc_mi355x_ipm_queue) reuses its per-slot workspaces and leaves no factor, so the re-solve cannot follow it.
+ * The call never writes ws (nor BAbt, RSQrq, DCt, d), so any number of re-solves may follow one IPM.
+ * Arrays: BAbt / RSQrq follow `lay` as in hpmpc_mi355x_ipm_batch (NULL: the packed default).  General constraints:
+ * unlike the other Part-2 calls this one takes a tile plan with ng > 0 (the tile plan of an OCP plan is one), with
+ * DCt problem-major in the plan's packed DCt layout (hpmpc_mi355x_ocp_offsets [17]); DCt may be null when every ng
+ * is 0.  Per set, nprob * nrhs of each: d, lam, t 32 doubles per stage, ux, pi 16 doubles per stage (the layouts of
+ * hpmpc_mi355x_ipm_batch); b 16 doubles per stage in state order (b_k over x_{k+1}), q 16 doubles per stage in
+ * variable order [r_k | q_k].  b or q null: every set of a problem takes that vector from the augmented row of the
+ * problem's BAbt_k / RSQrq_k.  scratch: nprob * nrhs * hpmpc_mi355x_kkt_scratch_doubles(plan) doubles, no
+ * initialisation needed.  compute_mult = 0: pi is not solved for and returns the IPM's previous iterate.
+ * Asynchronous on `stream`; synchronises with nothing (the first use of a layout uploads its stage table, as for
+ * every batched call).  Only the sets of problems [p0, p0+count) are read or written; count = 0 returns 0.
+ * nrhs < 1, a bad problem range, a null required pointer, a null DCt with ng > 0 or a refused launch return
+ * HPMPC_MI355X_EUNSUPPORTED and write nothing. */
+/* doubles of scratch per right-hand-side set */
+long long hpmpc_mi355x_kkt_scratch_doubles(const hpmpc_mi355x_plan *plan);
+int hpmpc_mi355x_kkt_new_rhs_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi355x_layout *lay, int nprob, int p0,
+                                   int count, int nrhs, const double *BAbt, const double *RSQrq, const double *DCt,
+                                   const double *b, const double *q, const double *d, double *ux, double *pi,
+                                   double *lam, double *t, const double *ws, double *scratch, int compute_mult,
+                                   void *stream);
+/* The batched core of fortran_order_ / c_order_d_solve_kkt_new_rhs_ocp_hard_tv: the call above with nrhs = 1 and null
+ * b / q on the packed default layout.  The whole wrapper is hpmpc_mi355x_ocp_pack_batch(matrices = 0) with the new
+ * b, q, r and bounds, this call (ux, pi, lam, t: the OCP iterate arrays), then hpmpc_mi355x_ocp_finish_batch.
+ * scratch: nprob * hpmpc_mi355x_kkt_scratch_doubles(hpmpc_mi355x_ocp_tile_plan(plan)) doubles. */
+int hpmpc_mi355x_ocp_kkt_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, int p0, int count, const double *BAbt,
+                               const double *RSQrq, const double *DCt, const double *d, double *ux, double *pi,
+                               double *lam, double *t, const double *ws, double *scratch, void *stream);
 
 #ifdef __cplusplus
 }
