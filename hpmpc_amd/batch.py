@@ -21,52 +21,10 @@ import os
 
 import numpy as np
 
+from .bindings import LIBPATH, check, lib, plan_args  # noqa: F401  (tests, tools and bench.py import LIBPATH from here)
 from .ocp import OCPQP
 
-_LIB = None
-# HPMPC_MI355X_LIB: another build of the same library (A/B timing of two builds on one box, tools/gpu_ab.sh)
-LIBPATH = os.environ.get("HPMPC_MI355X_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
-                                                             "libhpmpc_mi355x.so")
-
-
-def lib() -> C.CDLL:
-    """Load the in-tree HIP library (raises if it was not built)."""
-    global _LIB
-    if _LIB is None:
-        if not os.path.exists(LIBPATH):
-            raise RuntimeError(f"libhpmpc_mi355x.so not built ({LIBPATH}); run __graft_entry__.build()")
-        L = C.CDLL(LIBPATH, mode=os.RTLD_LOCAL | getattr(os, "RTLD_NOW", 2))
-        vp, i, d, ll = C.c_void_p, C.c_int, C.c_double, C.c_longlong
-        L.hpmpc_mi355x_plan_create.restype = vp
-        L.hpmpc_mi355x_plan_create.argtypes = [i, vp, vp, vp, vp, vp]
-        L.hpmpc_mi355x_plan_destroy.argtypes = [vp]
-        L.hpmpc_mi355x_ws_doubles.restype = ll
-        L.hpmpc_mi355x_ws_doubles.argtypes = [vp]
-        L.hpmpc_mi355x_ipm_solo.restype = i
-        L.hpmpc_mi355x_ipm_solo.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d, i, i, vp,
-                                            vp, vp, vp]
-        L.hpmpc_mi355x_ipm_batch.restype = i
-        L.hpmpc_mi355x_ipm_batch.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d, i, i, vp,
-                                             vp, vp, vp]
-        L.hpmpc_mi355x_ipm_pass.restype = i
-        L.hpmpc_mi355x_ipm_pass.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d, i, i, vp,
-                                            vp, vp, i, vp]
-        L.hpmpc_mi355x_ipm_batch_profiled.restype = i
-        L.hpmpc_mi355x_ipm_batch_profiled.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d, i,
-                                                      i, vp, vp, vp, vp, vp]
-        L.hpmpc_mi355x_ipm_queue.restype = i
-        L.hpmpc_mi355x_ipm_queue.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d, i, i,
-                                             vp, vp, vp, vp, vp, vp]
-        L.hpmpc_mi355x_ric_sv_batch.restype = i
-        L.hpmpc_mi355x_ric_sv_batch.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, i, i, vp, vp]
-        L.hpmpc_mi355x_ric_trf_batch.restype = i
-        L.hpmpc_mi355x_ric_trf_batch.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
-        L.hpmpc_mi355x_ric_trs_batch.restype = i
-        L.hpmpc_mi355x_ric_trs_batch.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, i, i, vp, vp]
-        L.hpmpc_mi355x_last_error.restype = i
-        L.hpmpc_mi355x_version.restype = C.c_char_p
-        _LIB = L
-    return _LIB
+kkt_lib = lib  # the batched KKT re-solve's calls are bound with every other one (hpmpc_amd.bindings)
 
 
 class _Layout(C.Structure):
@@ -152,31 +110,13 @@ def kkt_scratch_doubles(N: int) -> int:
     return (N + 1) * (6 * 16 + 4 * 32)
 
 
-_KKT_READY = False
-
-
-def kkt_lib() -> C.CDLL:
-    """The library with the argument types of the batched KKT re-solve declared (on first use, not in lib(): an
-    A/B library from before these calls, HPMPC_MI355X_LIB, still loads for everything else)."""
-    global _KKT_READY
-    L = lib()
-    if not _KKT_READY:
-        vp, i = C.c_void_p, C.c_int
-        L.hpmpc_mi355x_kkt_scratch_doubles.restype = C.c_longlong
-        L.hpmpc_mi355x_kkt_scratch_doubles.argtypes = [vp]
-        L.hpmpc_mi355x_kkt_new_rhs_batch.restype = i
-        L.hpmpc_mi355x_kkt_new_rhs_batch.argtypes = [vp, vp, i, i, i, i] + [vp] * 12 + [i, vp]
-        _KKT_READY = True
-    return L
-
-
 def kkt_buffers(torch, dev, plan, N: int, nprob: int, nrhs: int) -> dict:
     """Outputs and scratch of hpmpc_mi355x_kkt_new_rhs_batch for ``nrhs`` sets per problem: ux, pi (nprob, nrhs, N+1,
     16), lam, t (nprob, nrhs, N+1, 32), scratch (nprob, nrhs, hpmpc_mi355x_kkt_scratch_doubles)."""
     f64 = torch.float64
     new = lambda *shape: torch.zeros((nprob, nrhs) + shape, dtype=f64, device=dev)
     return dict(ux=new(N + 1, 16), pi=new(N + 1, 16), lam=new(N + 1, 32), t=new(N + 1, 32),
-                scratch=new(int(kkt_lib().hpmpc_mi355x_kkt_scratch_doubles(plan))))
+                scratch=new(int(lib().hpmpc_mi355x_kkt_scratch_doubles(plan))))
 
 
 def kkt_sets_call(torch, plan, layout, N, nprob, p0, count, nrhs, BAbt, RSQrq, DCt, b, q, d, out, ws, compute_mult,
@@ -193,7 +133,7 @@ def kkt_sets_call(torch, plan, layout, N, nprob, p0, count, nrhs, BAbt, RSQrq, D
         if tuple(out[name].shape) != (nprob, nrhs, N + 1, w):
             raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={nrhs}) expected")
     ptr = lambda x: None if x is None else x.data_ptr()
-    return kkt_lib().hpmpc_mi355x_kkt_new_rhs_batch(
+    return lib().hpmpc_mi355x_kkt_new_rhs_batch(
         plan, layout, nprob, p0, count, nrhs, ptr(BAbt), ptr(RSQrq), ptr(DCt), ptr(b), ptr(q), ptr(d), ptr(out["ux"]),
         ptr(out["pi"]), ptr(out["lam"]), ptr(out["t"]), ptr(ws), ptr(out["scratch"]), compute_mult, stream)
 
@@ -218,15 +158,8 @@ class BatchSolver:
         self.k_max = k_max
         self.dev = torch.device(device)
         L = lib()
-        self._keep = []
-        idx_arrs = [np.ascontiguousarray(i, dtype=np.int32) for i in qp.idxb]
-        self._keep.append(idx_arrs)
-        idxp = (C.POINTER(C.c_int) * (N + 1))(*[a.ctypes.data_as(C.POINTER(C.c_int)) for a in idx_arrs])
-        self._keep.append(idxp)
-        ints = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        self._nx, self._nu, self._nb, self._ng = ints(qp.nx), ints(qp.nu), ints(qp.nb), ints(qp.ng)
-        self.plan = L.hpmpc_mi355x_plan_create(N, self._nx.ctypes.data, self._nu.ctypes.data, self._nb.ctypes.data,
-                                               C.cast(idxp, C.c_void_p), self._ng.ctypes.data)
+        (nx, nu, nb, ng), idxp, self._keep = plan_args(qp.idxb, qp.nx, qp.nu, qp.nb, qp.ng)
+        self.plan = L.hpmpc_mi355x_plan_create(N, nx, nu, nb, idxp, ng)
         if not self.plan:
             raise ValueError(f"unsupported problem sizes for the GPU path (code {L.hpmpc_mi355x_last_error()})")
         # problem-major packed inputs
@@ -281,27 +214,24 @@ class BatchSolver:
     def _stream(self):
         return self.torch.cuda.current_stream(self.dev).cuda_stream
 
+    def _ipm(self, name, p0, count, opts, *tail):
+        """hpmpc_mi355x_<name> on problems [p0, p0 + count) with the arguments every batched IPM call shares
+        (opts: mu0, mu_tol, alpha_min, warm_start, compute_mult), then ``tail`` and torch's current stream."""
+        count = self.nprob - p0 if count is None else count
+        p = lambda x: x.data_ptr()
+        name = "hpmpc_mi355x_" + name
+        check(getattr(lib(), name)(
+            self.plan, C.byref(self.layout), self.nprob, p0, count, p(self.BAbt), p(self.RSQrq), p(self.d), p(self.ux),
+            p(self.pi), p(self.lam), p(self.t), p(self.ws), self.k_max, *opts, p(self.kk), p(self.ret), p(self.stat),
+            *tail, self._stream()), name)
+
     def ipm(self, *, mu0=2.0, mu_tol=1e-12, alpha_min=1e-8, warm_start=0, compute_mult=1, p0=0, count=None):
         """Batched d_ip2_res_mpc_hard_tv (asynchronous on torch's current stream)."""
-        count = self.nprob - p0 if count is None else count
-        rc = lib().hpmpc_mi355x_ipm_batch(
-            self.plan, C.byref(self.layout), self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
-            self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(),
-            self.ws.data_ptr(), self.k_max, mu0, mu_tol, alpha_min, warm_start, compute_mult, self.kk.data_ptr(),
-            self.ret.data_ptr(), self.stat.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ipm_batch failed ({rc})")
+        self._ipm("ipm_batch", p0, count, (mu0, mu_tol, alpha_min, warm_start, compute_mult))
 
     def ipm_solo(self, *, mu0=2.0, mu_tol=1e-12, alpha_min=1e-8, warm_start=0, compute_mult=1, p0=0, count=None):
         """ipm() as the latency path: each problem's whole solve in one launch (hpmpc_mi355x_ipm_solo)."""
-        count = self.nprob - p0 if count is None else count
-        rc = lib().hpmpc_mi355x_ipm_solo(
-            self.plan, C.byref(self.layout), self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
-            self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(),
-            self.ws.data_ptr(), self.k_max, mu0, mu_tol, alpha_min, warm_start, compute_mult, self.kk.data_ptr(),
-            self.ret.data_ptr(), self.stat.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ipm_solo failed ({rc})")
+        self._ipm("ipm_solo", p0, count, (mu0, mu_tol, alpha_min, warm_start, compute_mult))
 
     def kkt_buffers(self, nrhs: int = 1) -> dict:
         """The output and scratch tensors kkt_new_rhs(nrhs=nrhs) writes (allocated on first use, then reused)."""
@@ -321,36 +251,22 @@ class BatchSolver:
         Asynchronous on torch's current stream."""
         count = self.nprob - p0 if count is None else count
         out = self.kkt_buffers(nrhs)
-        rc = kkt_sets_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, nrhs, self.BAbt,
-                           self.RSQrq, None, b, q, d, out, self.ws, compute_mult, self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_kkt_new_rhs_batch failed ({rc})")
+        check(kkt_sets_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, nrhs, self.BAbt,
+                            self.RSQrq, None, b, q, d, out, self.ws, compute_mult, self._stream()),
+              "hpmpc_mi355x_kkt_new_rhs_batch")
         return out["ux"], out["pi"], out["lam"], out["t"]
 
     def ipm_pass(self, pss, *, mu0=2.0, mu_tol=1e-12, alpha_min=1e-8, warm_start=0, compute_mult=1, p0=0,
                  count=None):
         """One pass of the batched IPM (0 init, 1 factorisation, 2 predictor, 3 corrector, 4 update);
         ipm() == pass 0 then k_max rounds of passes 1..4."""
-        count = self.nprob - p0 if count is None else count
-        rc = lib().hpmpc_mi355x_ipm_pass(
-            self.plan, C.byref(self.layout), self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
-            self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(),
-            self.ws.data_ptr(), self.k_max, mu0, mu_tol, alpha_min, warm_start, compute_mult, self.kk.data_ptr(),
-            self.ret.data_ptr(), self.stat.data_ptr(), pss, self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ipm_pass failed ({rc})")
+        self._ipm("ipm_pass", p0, count, (mu0, mu_tol, alpha_min, warm_start, compute_mult), pss)
 
     def ipm_profiled(self, *, mu0=2.0, mu_tol=1e-12, alpha_min=1e-8, warm_start=0, compute_mult=1):
         """ipm() with hipEvents around every pass kernel (synchronous).  Returns the summed device time
         (ms) of passes [init, factorisation, predictor, corrector, update]."""
         out = np.zeros(5)
-        rc = lib().hpmpc_mi355x_ipm_batch_profiled(
-            self.plan, C.byref(self.layout), self.nprob, 0, self.nprob, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
-            self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(),
-            self.ws.data_ptr(), self.k_max, mu0, mu_tol, alpha_min, warm_start, compute_mult, self.kk.data_ptr(),
-            self.ret.data_ptr(), self.stat.data_ptr(), out.ctypes.data, self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ipm_batch_profiled failed ({rc})")
+        self._ipm("ipm_batch_profiled", 0, None, (mu0, mu_tol, alpha_min, warm_start, compute_mult), out.ctypes.data)
         return out
 
     def queue(self, nq: int, n_slots: int | None = None) -> "IpmQueue":
@@ -360,12 +276,10 @@ class BatchSolver:
     def ric_sv(self, *, compute_pi=1, compute_Pb=0, p0=0, count=None):
         """Batched d_back_ric_rec_sv_tv_res (nb = ng = 0, no update rows): factor into ws."""
         count = self.nprob - p0 if count is None else count
-        rc = lib().hpmpc_mi355x_ric_sv_batch(
+        check(lib().hpmpc_mi355x_ric_sv_batch(
             self.plan, C.byref(self.layout), self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
             self.ux.data_ptr(), self.pi.data_ptr(), self.ws.data_ptr(), compute_pi, compute_Pb,
-            self.Pb.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ric_sv_batch failed ({rc})")
+            self.Pb.data_ptr(), self._stream()), "hpmpc_mi355x_ric_sv_batch")
 
     def ric_sv_bound(self, stream=None, *, compute_pi=1, compute_Pb=0):
         """ric_sv over the whole batch as a zero-argument callable with every argument marshalled once (a stream
@@ -381,21 +295,17 @@ class BatchSolver:
     def ric_trf(self, *, p0=0, count=None):
         """Batched d_back_ric_rec_trf_tv_res (nb = ng = 0): factor into ws."""
         count = self.nprob - p0 if count is None else count
-        rc = lib().hpmpc_mi355x_ric_trf_batch(self.plan, C.byref(self.layout), self.nprob, p0, count,
-                                              self.BAbt.data_ptr(), self.RSQrq.data_ptr(), self.ws.data_ptr(),
-                                              self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ric_trf_batch failed ({rc})")
+        check(lib().hpmpc_mi355x_ric_trf_batch(self.plan, C.byref(self.layout), self.nprob, p0, count,
+                                               self.BAbt.data_ptr(), self.RSQrq.data_ptr(), self.ws.data_ptr(),
+                                               self._stream()), "hpmpc_mi355x_ric_trf_batch")
 
     def ric_trs(self, b, q, *, compute_pi=1, compute_Pb=1, p0=0, count=None):
         """Batched d_back_ric_rec_trs_tv_res with the factor left in ws by ric_sv."""
         count = self.nprob - p0 if count is None else count
-        rc = lib().hpmpc_mi355x_ric_trs_batch(
+        check(lib().hpmpc_mi355x_ric_trs_batch(
             self.plan, C.byref(self.layout), self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
             b.data_ptr(), q.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(), self.ws.data_ptr(), compute_pi,
-            compute_Pb, self.Pb.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ric_trs_batch failed ({rc})")
+            compute_Pb, self.Pb.data_ptr(), self._stream()), "hpmpc_mi355x_ric_trs_batch")
 
 
 def algorithmic_bytes_per_ip_iter(qp: OCPQP) -> float:
@@ -556,6 +466,5 @@ class IpmQueue:
             self.ws.data_ptr(), self.qctl.data_ptr(), s.k_max, mu0, mu_tol, alpha_min, warm_start, compute_mult,
             self.kk.data_ptr(), self.ret.data_ptr(), self.stat.data_ptr(), out.ctypes.data if profiled else None,
             C.byref(ticks), s._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ipm_queue failed ({rc})")
+        check(rc, "hpmpc_mi355x_ipm_queue")
         return (out if profiled else None), ticks.value

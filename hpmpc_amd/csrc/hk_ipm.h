@@ -277,7 +277,7 @@ __device__ double update_p2_pass(const RicIO& io, const BoxCtx& bc, const signed
             gst(res_d, b.up, v[j][15] - x - tu, b.ok && b.box);
             // r_m = lam t is re-formed at use by every phase-2 pass (and the corrector stores its own centred
             // r_m before its forward reads it): only the KKT re-solve and the general-constraint halves load
-            // this store, and the queue API has neither (BKP = false; layout_apply refuses ng > 0)
+            // this store, and the queue API has neither (BKP = false; batch_args refuses ng > 0)
             if (BKP) {
                 gst(res_m, b.lo, rml, b.ok);
                 gst(res_m, b.up, rmu, b.ok);

@@ -94,6 +94,11 @@ __device__ __forceinline__ LdsTabs lds_tables(const KArgs& a) {
     return T;
 }
 
+// Dynamic LDS of a kernel that calls lds_tables: Scratch, then per stage StageInfo, 16 + 16 table bytes and the
+// certificate bound.  The host's horizon limit (plan_supported) is computed from the same two constants.
+static_assert(LDS_FIXED == sizeof(Scratch) && LDS_PER_STAGE == sizeof(StageInfo) + 40, "hpmpc_kargs.h LDS constants");
+constexpr size_t lds_table_bytes(int N) { return LDS_FIXED + (size_t)(N + 1) * LDS_PER_STAGE; }
+
 __device__ __forceinline__ RicIO make_io(const KArgs& a, const LdsTabs& T, int p, double* F) {
     RicIO io;
     io.N = a.N;

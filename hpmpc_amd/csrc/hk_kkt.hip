@@ -50,7 +50,7 @@ template <class FX>
 static int kkt_rhs_launch_t(const KArgs* a, const KktArgs* x, int count, hipStream_t stream) {
     // the launch guard (hk_launch_guard.h): LDS tables, private segment against the stack limit, launch bound
     static const HkKernelLimits lim(reinterpret_cast<const void*>(&hk_kkt_rhs<FX>));
-    const size_t lds = sizeof(Scratch) + (size_t)(a->N + 1) * (sizeof(StageInfo) + 40);
+    const size_t lds = lds_table_bytes(a->N);
     if (const int e = lim.check(lds, 64)) return e;
     hipLaunchKernelGGL(hk_kkt_rhs<FX>, dim3((unsigned)count * (unsigned)x->nrhs), dim3(64), lds, stream, *a, *x);
     return (int)hipGetLastError();
@@ -59,9 +59,7 @@ static int kkt_rhs_launch_t(const KArgs* a, const KktArgs* x, int count, hipStre
 // The compiled inner-stage class is the tile plan's (KArgs.fixcls), as in hk_launch.
 extern "C" int hk_kkt_rhs_launch(const KArgs* a, const KktArgs* x, int count, hipStream_t stream) {
     if (count <= 0 || x->nrhs <= 0) return 0;
-    switch (a->fixcls) {
-        case 1: return kkt_rhs_launch_t<FixSh<4, 12>>(a, x, count, stream);
-        case 2: return kkt_rhs_launch_t<FixSh<3, 8>>(a, x, count, stream);
-        default: return kkt_rhs_launch_t<NoFix>(a, x, count, stream);
-    }
+    return with_fixcls(a->fixcls, [&](auto fx) {
+        return kkt_rhs_launch_t<typename decltype(fx)::type>(a, x, count, stream);
+    });
 }

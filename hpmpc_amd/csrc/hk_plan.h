@@ -1,8 +1,9 @@
-// hk_plan.h -- the tile path's plan and the one-problem staging carve, shared by the host files of that path:
-// hpmpc_capi.cpp (plan, layout tables, batched API; defines the plan functions below), hpmpc_capi_queue.cpp (the
-// problem queue), hpmpc_capi_dropin.cpp (reference-named hard-constraint entry points; defines the arena functions)
-// hpmpc_capi_soft.cpp (soft-constraint IPM and residual; defines the soft refusals and layout),
-// hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM) and hpmpc_capi_kkt.cpp (the batched KKT re-solve).
+// hk_plan.h -- the tile path's plan, the device tables and call checks of its batched API and the one-problem staging
+// carve, shared by the host files of that path: hpmpc_capi.cpp (plan, layout tables, batched API; defines the plan
+// functions and call checks below), hpmpc_capi_queue.cpp (the problem queue), hpmpc_capi_dropin.cpp (reference-named
+// hard-constraint entry points; defines the arena functions), hpmpc_capi_soft.cpp (soft-constraint IPM and residual;
+// defines the soft refusals, layout and IPM setup), hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM),
+// hpmpc_capi_ocp.cpp (the batched OCP front end) and hpmpc_capi_kkt.cpp (the batched KKT re-solve).
 #pragma once
 #include <mutex>
 #include <vector>
@@ -15,6 +16,26 @@ struct StageInfoH {  // mirror of hk::StageInfo
     int nu, nx, nb, ng, xo, nx1, nu1, xo1, sdB, sdR, oB, oR, oD, pnb, r0, oG;
 };
 
+// The device copy of a host array: allocated and filled by upload(), freed with its owner, never rewritten.
+template <class T>
+class DevTable {
+    T* d_ = nullptr;
+
+public:
+    DevTable() = default;
+    DevTable(DevTable&& o) noexcept : d_(o.d_) { o.d_ = nullptr; }
+    DevTable(const DevTable&) = delete;
+    DevTable& operator=(const DevTable&) = delete;
+    ~DevTable() {
+        if (d_) (void)hipFree(d_);
+    }
+    bool upload(const std::vector<T>& h, const char* what) {
+        return hip_ok(hipMalloc((void**)&d_, sizeof(T) * h.size()), what) &&
+               hip_ok(hipMemcpy(d_, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice), what);
+    }
+    const T* get() const { return d_; }
+};
+
 // Plan: stage tables shared by every problem of a batch.
 struct hpmpc_mi355x_plan {
     int N = 0;
@@ -24,17 +45,18 @@ struct hpmpc_mi355x_plan {
     std::vector<signed char> tileslot, slotvar;
     std::vector<long long> offB, offR;  // packed default layout
     long long packB = 0, packR = 0;
-    void* d_st = nullptr;  // the stage table of the packed default layout (uploaded once, never rewritten)
-    signed char *d_tileslot = nullptr, *d_slotvar = nullptr;
+    DevTable<StageInfoH> d_st;  // the stage table of the packed default layout
+    DevTable<signed char> d_tileslot, d_slotvar;
     // one device stage table per caller layout (hpmpc_mi355x_layout: offsets and shared-block flags differ), uploaded
     // the first time a layout is used and never rewritten: a launch still running on another stream keeps reading its
     // own layout's offsets while the next call uses a different one
     struct LayoutTable {
         std::vector<StageInfoH> st;
-        void* d = nullptr;
+        DevTable<StageInfoH> d;
     };
-    std::vector<LayoutTable> ltabs;  // at most kMaxLayouts, guarded by ltabs_mu (calls on one plan from several threads)
-    std::mutex ltabs_mu;
+    // at most kMaxLayouts, guarded by ltabs_mu (calls on one plan from several threads); a cache: a const plan fills it
+    mutable std::vector<LayoutTable> ltabs;
+    mutable std::mutex ltabs_mu;
     int fixcls = 0;                             // compiled inner-stage class (kernel instance)
     int nbt = 0;                                // sum of nb + ng
     int ngt = 0;                                // sum of ng
@@ -53,10 +75,21 @@ inline long long ws_doubles(int N) {
 // hpmpc_capi.cpp
 bool plan_supported(int N, const int* nx, const int* nu, const int* nb, const int* const* idxb, const int* ng,
                     const char** why);
-KArgs base_args(const hpmpc_mi355x_plan* P, int nprob, int p0);
-bool layout_apply(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a);
-// layout_apply without its ng > 0 refusal, for the calls that carry a DCt array (hpmpc_capi_kkt.cpp)
-bool layout_set(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a);
+// 16 ints per stage: out[16 k + l] = idxb[k][l] for l < nb[k]; the other entries of `out` are left as they are
+void idxb_table(int N, const int* nb, const int* const* idxb, int* out);
+// The checks every batched call with a problem range makes, each setting HPMPC_MI355X_EUNSUPPORTED with one stderr
+// line.  range_ok: a plan, nprob > 0 and 0 <= p0, 0 <= count, p0 + count <= nprob (without int overflow);
+// null_array returns the code.  launch_error maps a launcher's nonzero return: HK_LAUNCH_REFUSED to
+// HPMPC_MI355X_EUNSUPPORTED, anything else to HPMPC_MI355X_EHIP, and returns the code.
+bool range_ok(const void* plan, int nprob, int p0, int count, const char* who);
+int null_array(const char* who);
+int launch_error(int e, const char* what);
+// The argument block of a batched call: the plan's tables and strides, the layout (null: the packed default; a
+// layout's first use uploads its stage table) and DCt.  A call that carries no DCt array refuses a plan with
+// ng > 0 (DCT_NONE); one that does passes it on when the plan has general constraints (DCT_ARRAY).  False: g_err set.
+enum DctPolicy { DCT_NONE, DCT_ARRAY };
+bool batch_args(KArgs& a, const hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, int nprob, int p0,
+                DctPolicy policy, const double* DCt = nullptr);
 int launch(int which, const KArgs* a, int count, hipStream_t s);  // hk_launch, or the ric2 variant's two-wave sv
 // the IPM fields of `a` (plan tables and layout already set) and the launch `which`: shared by every batched IPM call
 int ipm_run(KArgs& a, int count, const double* BAbt, const double* RSQrq, const double* d, double* ux, double* pi,
@@ -89,6 +122,12 @@ struct SoftLayout {
     long sC = 0, sD = 0, sZ = 0;  // doubles per problem of t / lam, d, Z / z
     long sF = 0;                  // the flat Qx / qx | Zl / zl block with the reference's padding
 };
+// What d_ip2_mpc_soft_tv and the batched soft IPM set alike: 1 / sum(2 nb + 4 ns) (0: no constraint anywhere), the
+// Riccati flags of their sv / trs steps, and the scalar fields of a zeroed SoftArgs
+double soft_mu_scal(int N, const int* nb, const int* ns);
+void soft_ric_flags(KArgs& a, int compute_mult);
+SoftArgs soft_scalars(int N, int nprob, int p0, int k_max, int warm_start, double mu0, double mu_tol, double alpha_min,
+                      double mu_scal);
 // ng > 0, nu[N] != 0, N < 1, or a b_k the reference reads outside BAbt_k
 const char* soft_unsupported(int N, const int* nx, const int* nu, const int* ng);
 // the layout; refuses the stray soft-gradient write into a Zl its pass still reads

@@ -463,9 +463,7 @@ static int launch2_t(const KArgs* a, int count, hipStream_t stream) {
 extern "C" int hk_launch_ric2(int which, const KArgs* a, int count, hipStream_t stream) {
     if (count <= 0) return 0;
     if (which != K_SV) return HK_LAUNCH_REFUSED;
-    switch (a->fixcls) {
-        case 1: return launch2_t<FixSh<4, 12>>(a, count, stream);
-        case 2: return launch2_t<FixSh<3, 8>>(a, count, stream);
-        default: return launch2_t<NoFix>(a, count, stream);
-    }
+    return with_fixcls(a->fixcls, [&](auto fx) {
+        return launch2_t<typename decltype(fx)::type>(a, count, stream);
+    });
 }

@@ -655,6 +655,24 @@ struct NoFix {  // generic kernels: no compile-time stage class
     __device__ __forceinline__ explicit NoFix(const StageRef&) {}
 };
 
+// Host side, the one place that names the compiled inner-stage classes (KArgs.fixcls): 0 generic, 1 nu=4 nx=12,
+// 2 nu=3 nx=8.  fixcls_of is hk_fixcls (the plan picks the class and flags its stages, StageInfo.r0; any other
+// problem runs the generic kernels); with_fixcls gives every launcher the class type to instantiate its kernels
+// for: f is a generic lambda called as f(FxTag<FX>{}), FX = typename decltype(tag)::type.
+inline int fixcls_of(int nu, int nx) { return nu == 4 && nx == 12 ? 1 : nu == 3 && nx == 8 ? 2 : 0; }
+template <class FX>
+struct FxTag {
+    using type = FX;
+};
+template <class F>
+int with_fixcls(int fixcls, F&& f) {
+    switch (fixcls) {
+        case 1: return f(FxTag<FixSh<4, 12>>{});
+        case 2: return f(FxTag<FixSh<3, 8>>{});
+        default: return f(FxTag<NoFix>{});
+    }
+}
+
 // Run f(sh) with the stage's shape object: the constant one when the stage belongs to FX's class.
 template <class FX, class F>
 __device__ __forceinline__ void with_shape(const StageInfo& s, F&& f) {

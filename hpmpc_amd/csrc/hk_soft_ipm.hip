@@ -126,7 +126,7 @@ template <class FX>
 static int soft_ipm_launch_t(const KArgs* a, const SoftArgs* s, int count, hipStream_t stream) {
     // the launch guard (hk_launch_guard.h): LDS tables, private segment against the stack limit, launch bound
     static const HkKernelLimits lim(reinterpret_cast<const void*>(&hk_soft_ipm<FX>));
-    const size_t lds = sizeof(Scratch) + (size_t)(a->N + 1) * (sizeof(StageInfo) + 40);
+    const size_t lds = lds_table_bytes(a->N);
     if (const int e = lim.check(lds, 64)) return e;
     hipLaunchKernelGGL(hk_soft_ipm_init, dim3(count), dim3(64), 0, stream, *a, *s);
     hipLaunchKernelGGL(hk_soft_ipm<FX>, dim3(count), dim3(64), lds, stream, *a, *s);
@@ -136,9 +136,7 @@ static int soft_ipm_launch_t(const KArgs* a, const SoftArgs* s, int count, hipSt
 // The compiled inner-stage class is the tile plan's (KArgs.fixcls), as in hk_launch.
 extern "C" int hk_soft_ipm_launch(const KArgs* a, const SoftArgs* s, int count, hipStream_t stream) {
     if (count <= 0) return 0;
-    switch (a->fixcls) {
-        case 1: return soft_ipm_launch_t<FixSh<4, 12>>(a, s, count, stream);
-        case 2: return soft_ipm_launch_t<FixSh<3, 8>>(a, s, count, stream);
-        default: return soft_ipm_launch_t<NoFix>(a, s, count, stream);
-    }
+    return with_fixcls(a->fixcls, [&](auto fx) {
+        return soft_ipm_launch_t<typename decltype(fx)::type>(a, s, count, stream);
+    });
 }

@@ -40,9 +40,9 @@ int launch(int which, const KArgs* a, int count, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 bool plan_supported(int N, const int* nx, const int* nu, const int* nb, const int* const* idxb, const int* ng,
                     const char** why) {
-    // the tile kernels stage the plan's tables in LDS, 256 B + 104 B per stage (hpmpc_kernels.hip launch_t: Scratch +
-    // StageInfo + tile / slot tables + the certificate bounds), within the 160 KiB one workgroup may use
-    if (256 + 104LL * (N + 1) > 160 * 1024) {
+    // the tile kernels stage the plan's tables in LDS (lds_table_bytes, hk_ipm_body.h: Scratch + per stage StageInfo,
+    // tile / slot tables and the certificate bound), within the 160 KiB one workgroup may use
+    if (LDS_FIXED + (long long)LDS_PER_STAGE * (N + 1) > 160 * 1024) {
         *why = "horizon beyond the LDS stage tables of the tile kernels (N <= 1571)";
         return false;
     }
@@ -82,7 +82,7 @@ bool plan_supported(int N, const int* nx, const int* nu, const int* nb, const in
 // The device stage table for the given stage offsets and shared-block flags (StageInfo r0 bits 1 / 2: the block of
 // stage k sits at the batch's base + offset for every problem): the plan's default table when they are the packed
 // defaults, else the table of that layout (uploaded on first use, cached for the plan's lifetime).
-static const void* plan_stage_table(hpmpc_mi355x_plan* P, const long long* offB, const long long* offR,
+static const void* plan_stage_table(const hpmpc_mi355x_plan* P, const long long* offB, const long long* offR,
                                     const unsigned char* shB = nullptr, const unsigned char* shR = nullptr) {
     const int N = P->N;
     std::vector<StageInfoH> st = P->st;
@@ -92,10 +92,10 @@ static const void* plan_stage_table(hpmpc_mi355x_plan* P, const long long* offB,
         st[k].r0 = (P->st[k].r0 & 1) | ((shB && k < N && shB[k]) ? 2 : 0) | ((shR && shR[k]) ? 4 : 0);
     }
     const size_t bytes = sizeof(StageInfoH) * (N + 1);
-    if (!memcmp(st.data(), P->st.data(), bytes)) return P->d_st;
+    if (!memcmp(st.data(), P->st.data(), bytes)) return P->d_st.get();
     std::lock_guard<std::mutex> lock(P->ltabs_mu);
     for (const auto& t : P->ltabs)
-        if (!memcmp(st.data(), t.st.data(), bytes)) return t.d;
+        if (!memcmp(st.data(), t.st.data(), bytes)) return t.d.get();
     // each distinct layout keeps a device table (and its first use a synchronous upload) until the plan is destroyed:
     // a caller whose offsets change from call to call would grow it without bound, so the cache is capped
     constexpr size_t kMaxLayouts = 64;
@@ -104,14 +104,10 @@ static const void* plan_stage_table(hpmpc_mi355x_plan* P, const long long* offB,
                                            "family, or keep the offsets fixed)");
         return nullptr;
     }
-    void* d = nullptr;
-    if (!hip_ok(hipMalloc(&d, bytes), "layout stage table")) return nullptr;
-    if (!hip_ok(hipMemcpy(d, st.data(), bytes, hipMemcpyHostToDevice), "layout stage table")) {
-        (void)hipFree(d);
-        return nullptr;
-    }
-    P->ltabs.push_back({std::move(st), d});
-    return d;
+    DevTable<StageInfoH> d;
+    if (!d.upload(st, "layout stage table")) return nullptr;
+    P->ltabs.push_back({std::move(st), std::move(d)});
+    return P->ltabs.back().d.get();
 }
 
 extern "C" hpmpc_mi355x_plan* hpmpc_mi355x_plan_create(int N, const int* nx, const int* nu, const int* nb,
@@ -188,27 +184,20 @@ extern "C" hpmpc_mi355x_plan* hpmpc_mi355x_plan_create(int N, const int* nx, con
         P->st[k].oB = k < N ? (int)P->offB[k] : 0;
         P->st[k].oR = (int)P->offR[k];
     }
-    bool ok = hip_ok(hipMalloc(&P->d_st, sizeof(StageInfoH) * (N + 1)), "plan alloc") &&
-              hip_ok(hipMalloc((void**)&P->d_tileslot, (N + 1) * 16), "plan alloc") &&
-              hip_ok(hipMalloc((void**)&P->d_slotvar, (N + 1) * 16), "plan alloc") &&
-              hip_ok(hipMemcpy(P->d_tileslot, P->tileslot.data(), (N + 1) * 16, hipMemcpyHostToDevice), "plan") &&
-              hip_ok(hipMemcpy(P->d_slotvar, P->slotvar.data(), (N + 1) * 16, hipMemcpyHostToDevice), "plan") &&
-              hip_ok(hipMemcpy(P->d_st, P->st.data(), sizeof(StageInfoH) * (N + 1), hipMemcpyHostToDevice), "plan");
-    if (!ok) {
-        hpmpc_mi355x_plan_destroy(P);
+    if (!P->d_st.upload(P->st, "plan tables") || !P->d_tileslot.upload(P->tileslot, "plan tables") ||
+        !P->d_slotvar.upload(P->slotvar, "plan tables")) {
+        delete P;
         return nullptr;
     }
     g_err = 0;
     return P;
 }
 
-extern "C" void hpmpc_mi355x_plan_destroy(hpmpc_mi355x_plan* P) {
-    if (!P) return;
-    if (P->d_st) (void)hipFree(P->d_st);
-    for (auto& t : P->ltabs) (void)hipFree(t.d);
-    if (P->d_tileslot) (void)hipFree(P->d_tileslot);
-    if (P->d_slotvar) (void)hipFree(P->d_slotvar);
-    delete P;
+extern "C" void hpmpc_mi355x_plan_destroy(hpmpc_mi355x_plan* P) { delete P; }
+
+void idxb_table(int N, const int* nb, const int* const* idxb, int* out) {
+    for (int k = 0; k <= N; k++)
+        for (int l = 0; l < nb[k]; l++) out[k * 16 + l] = idxb[k][l];
 }
 
 extern "C" long long hpmpc_mi355x_ws_doubles(const hpmpc_mi355x_plan* P) { return P ? ws_doubles(P->N) : 0; }
@@ -228,15 +217,51 @@ extern "C" const char* hpmpc_mi355x_version(void) {
     return "hpmpc_mi355x 0.1 gfx950 (wave-per-problem, f64 MFMA 16x16x4 stage contractions)";
 }
 
-KArgs base_args(const hpmpc_mi355x_plan* P, int nprob, int p0) {
-    KArgs a;
+bool range_ok(const void* plan, int nprob, int p0, int count, const char* who) {
+    if (plan && nprob > 0 && p0 >= 0 && count >= 0 && (long long)p0 + count <= nprob) return true;
+    char msg[128];
+    snprintf(msg, sizeof msg, "%s: plan or problem range", who);
+    hk_set_error(HPMPC_MI355X_EUNSUPPORTED, msg);
+    return false;
+}
+
+int null_array(const char* who) {
+    char msg[128];
+    snprintf(msg, sizeof msg, "%s: a required array is null", who);
+    hk_set_error(HPMPC_MI355X_EUNSUPPORTED, msg);
+    return g_err;
+}
+
+int launch_error(int e, const char* what) {
+    hk_set_error(e == HK_LAUNCH_REFUSED ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP, what);
+    return g_err;
+}
+
+bool batch_args(KArgs& a, const hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, int nprob, int p0,
+                DctPolicy policy, const double* DCt) {
+    if (!P) {
+        g_err = HPMPC_MI355X_EUNSUPPORTED;
+        return false;
+    }
+    if (policy == DCT_NONE && P->ngt) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "batched entry points: general constraints (ng > 0) need the "
+                                           "reference-named entry points");
+        return false;
+    }
     memset(&a, 0, sizeof a);
     a.N = P->N;
     a.nprob = nprob;
     a.p0 = p0;
-    a.st = P->d_st;
-    a.tileslot = P->d_tileslot;
-    a.slotvar = P->d_slotvar;
+    a.st = P->d_st.get();
+    a.tileslot = P->d_tileslot.get();
+    a.slotvar = P->d_slotvar.get();
+    if (lay && lay->BAbt_off && lay->RSQrq_off) {
+        a.st = plan_stage_table(P, lay->BAbt_off, lay->RSQrq_off, lay->BAbt_shared, lay->RSQrq_shared);
+        if (!a.st) return false;
+    }
+    a.sB = lay ? lay->BAbt_stride : P->packB;
+    a.sR = lay ? lay->RSQrq_stride : P->packR;
+    a.DCt = P->ngt ? DCt : nullptr;
     a.sV16 = (long long)(P->N + 1) * V16;
     a.sV32 = (long long)(P->N + 1) * V32;
     a.sW = ws_doubles(P->N);
@@ -245,25 +270,6 @@ KArgs base_args(const hpmpc_mi355x_plan* P, int nprob, int p0) {
     a.ngt = P->ngt;
     a.sG = P->packG;
     a.dbg = g_dbg_buf;
-    return a;
-}
-
-bool layout_apply(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a) {
-    if (P->ngt) {  // the batched entry points carry no DCt array
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "batched entry points: general constraints (ng > 0) need the "
-                                           "reference-named entry points");
-        return false;
-    }
-    return layout_set(P, lay, a);
-}
-
-bool layout_set(hpmpc_mi355x_plan* P, const hpmpc_mi355x_layout* lay, KArgs& a) {
-    if (lay && lay->BAbt_off && lay->RSQrq_off) {
-        a.st = plan_stage_table(P, lay->BAbt_off, lay->RSQrq_off, lay->BAbt_shared, lay->RSQrq_shared);
-        if (!a.st) return false;
-    }
-    a.sB = lay ? lay->BAbt_stride : P->packB;
-    a.sR = lay ? lay->RSQrq_stride : P->packR;
     return true;
 }
 
@@ -316,11 +322,7 @@ int ipm_run(KArgs& a, int count, const double* BAbt, const double* RSQrq, const 
     a.kk = kk;
     a.ret = ret;
     a.stat = stat;
-    int e = hk_launch(which, &a, count, (hipStream_t)stream);
-    if (e) {
-        hk_set_error(HPMPC_MI355X_EHIP, "hk_ipm launch failed");
-        return HPMPC_MI355X_EHIP;
-    }
+    if (const int e = hk_launch(which, &a, count, (hipStream_t)stream)) return launch_error(e, "hk_ipm launch failed");
     return g_err = 0;
 }
 
@@ -330,10 +332,8 @@ int ipm_launch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, in
                const double* BAbt, const double* RSQrq, const double* d, double* ux, double* pi, double* lam,
                double* t, double* ws, int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
                int compute_mult, int* kk, int* ret, double* stat, int which, void* stream) {
-    auto* P = const_cast<hpmpc_mi355x_plan*>(plan);
-    if (!P) return g_err = HPMPC_MI355X_EUNSUPPORTED;
-    KArgs a = base_args(P, nprob, p0);
-    if (!layout_apply(P, lay, a)) return g_err;
+    KArgs a;
+    if (!batch_args(a, plan, lay, nprob, p0, DCT_NONE)) return g_err;
     return ipm_run(a, count, BAbt, RSQrq, d, ux, pi, lam, t, ws, k_max, mu0, mu_tol, alpha_min, warm_start,
                    compute_mult, kk, ret, stat, which, stream);
 }
@@ -423,10 +423,8 @@ extern "C" int hpmpc_mi355x_ric_sv_batch(const hpmpc_mi355x_plan* plan, const hp
                                          int p0, int count, const double* BAbt, const double* RSQrq, double* ux,
                                          double* pi, double* ws, int compute_pi, int compute_Pb, double* Pb,
                                          void* stream) {
-    auto* P = const_cast<hpmpc_mi355x_plan*>(plan);
-    if (!P) return g_err = HPMPC_MI355X_EUNSUPPORTED;
-    KArgs a = base_args(P, nprob, p0);
-    if (!layout_apply(P, lay, a)) return g_err;
+    KArgs a;
+    if (!batch_args(a, plan, lay, nprob, p0, DCT_NONE)) return g_err;
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
     a.ux = ux;
@@ -435,29 +433,20 @@ extern "C" int hpmpc_mi355x_ric_sv_batch(const hpmpc_mi355x_plan* plan, const hp
     a.compute_pi = compute_pi;
     a.compute_Pb = compute_Pb && Pb;
     a.vPb = Pb;
-    int e = launch(K_SV, &a, count, (hipStream_t)stream);
-    if (e) {
-        hk_set_error(HPMPC_MI355X_EHIP, "hk_ric_sv launch failed");
-        return HPMPC_MI355X_EHIP;
-    }
+    if (const int e = launch(K_SV, &a, count, (hipStream_t)stream)) return launch_error(e, "hk_ric_sv launch failed");
     return g_err = 0;
 }
 
 extern "C" int hpmpc_mi355x_ric_trf_batch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob,
                                           int p0, int count, const double* BAbt, const double* RSQrq, double* ws,
                                           void* stream) {
-    auto* P = const_cast<hpmpc_mi355x_plan*>(plan);
-    if (!P) return g_err = HPMPC_MI355X_EUNSUPPORTED;
-    KArgs a = base_args(P, nprob, p0);
-    if (!layout_apply(P, lay, a)) return g_err;
+    KArgs a;
+    if (!batch_args(a, plan, lay, nprob, p0, DCT_NONE)) return g_err;
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
     a.ws = ws;
-    int e = hk_launch(K_TRF, &a, count, (hipStream_t)stream);
-    if (e) {
-        hk_set_error(HPMPC_MI355X_EHIP, "hk_ric_trf launch failed");
-        return HPMPC_MI355X_EHIP;
-    }
+    if (const int e = hk_launch(K_TRF, &a, count, (hipStream_t)stream))
+        return launch_error(e, "hk_ric_trf launch failed");
     return g_err = 0;
 }
 
@@ -465,10 +454,8 @@ extern "C" int hpmpc_mi355x_ric_trs_batch(const hpmpc_mi355x_plan* plan, const h
                                           int p0, int count, const double* BAbt, const double* RSQrq, const double* b,
                                           const double* q, double* ux, double* pi, double* ws, int compute_pi,
                                           int compute_Pb, double* Pb, void* stream) {
-    auto* P = const_cast<hpmpc_mi355x_plan*>(plan);
-    if (!P) return g_err = HPMPC_MI355X_EUNSUPPORTED;
-    KArgs a = base_args(P, nprob, p0);
-    if (!layout_apply(P, lay, a)) return g_err;
+    KArgs a;
+    if (!batch_args(a, plan, lay, nprob, p0, DCT_NONE)) return g_err;
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
     a.vb = b;
@@ -479,11 +466,8 @@ extern "C" int hpmpc_mi355x_ric_trs_batch(const hpmpc_mi355x_plan* plan, const h
     a.compute_pi = compute_pi;
     a.compute_Pb = compute_Pb;
     a.vPb = Pb;
-    int e = hk_launch(K_TRS, &a, count, (hipStream_t)stream);
-    if (e) {
-        hk_set_error(HPMPC_MI355X_EHIP, "hk_ric_trs launch failed");
-        return HPMPC_MI355X_EHIP;
-    }
+    if (const int e = hk_launch(K_TRS, &a, count, (hipStream_t)stream))
+        return launch_error(e, "hk_ric_trs launch failed");
     return g_err = 0;
 }
 

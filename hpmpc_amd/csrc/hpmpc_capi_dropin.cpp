@@ -49,12 +49,10 @@ Arena arena(const hpmpc_mi355x_plan* P, int k_max) {
 }
 
 KArgs arena_args(const hpmpc_mi355x_plan* P, const Arena& A, double* dev) {
-    KArgs a = base_args(P, 1, 0);
-    a.sB = P->packB;
-    a.sR = P->packR;
+    KArgs a;
+    (void)batch_args(a, P, nullptr, 1, 0, DCT_ARRAY, dev + A.DCt);  // the packed default layout: nothing to refuse
     a.BAbt = dev + A.BAbt;
     a.RSQ = dev + A.RSQ;
-    a.DCt = P->ngt ? dev + A.DCt : nullptr;
     a.d = dev + A.d;
     a.ux = dev + A.ux;
     a.pi = dev + A.pi;

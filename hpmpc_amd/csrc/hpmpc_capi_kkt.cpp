@@ -3,11 +3,10 @@
 // right-hand-side sets per problem in one launch of hk_kkt_rhs (hk_kkt.hip).  The workspaces an IPM left
 // (hpmpc_mi355x_ipm_batch, _ipm_solo, _ocp_ipm_batch) are read only; each set's work vectors live in the caller's
 // scratch (kkt_scratch_doubles, hk_kkt_args.h).  The core call carries a DCt array, so it takes tile plans with
-// general constraints and sets the layout through layout_set, not through layout_apply's ng > 0 refusal.
+// general constraints (batch_args with DCT_ARRAY).
 #include <climits>
 
 #include "hk_kkt_args.h"
-#include "hk_launch_guard.h"
 #include "hk_plan.h"
 
 extern "C" long long hpmpc_mi355x_kkt_scratch_doubles(const hpmpc_mi355x_plan* P) {
@@ -20,25 +19,22 @@ extern "C" int hpmpc_mi355x_kkt_new_rhs_batch(const hpmpc_mi355x_plan* plan, con
                                               double* ux, double* pi, double* lam, double* t, const double* ws,
                                               double* scratch, int compute_mult, void* stream) {
     g_err = 0;
-    auto* P = const_cast<hpmpc_mi355x_plan*>(plan);
+    const char* who = "hpmpc_mi355x_kkt_new_rhs_batch";
+    if (!range_ok(plan, nprob, p0, count, who)) return g_err;
     // the grid is count * nrhs workgroups and a set index is an int
-    if (!P || nprob <= 0 || p0 < 0 || count < 0 || (long long)p0 + count > nprob || nrhs < 1 ||
-        (long long)nprob * nrhs > INT_MAX) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_kkt_new_rhs_batch: plan, problem range or nrhs");
+    if (nrhs < 1 || (long long)nprob * nrhs > INT_MAX) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_kkt_new_rhs_batch: nrhs");
         return g_err;
     }
     if (count == 0) return 0;
-    if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !ws || !scratch || (P->ngt && !DCt)) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_kkt_new_rhs_batch: a required array is null");
-        return g_err;
-    }
-    KArgs a = base_args(P, nprob, p0);
-    if (!layout_set(P, lay, a)) return g_err;
+    if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !ws || !scratch || (plan->ngt && !DCt))
+        return null_array(who);
+    KArgs a;
+    if (!batch_args(a, plan, lay, nprob, p0, DCT_ARRAY, DCt)) return g_err;
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
-    a.DCt = P->ngt ? DCt : nullptr;
     a.ws = const_cast<double*>(ws);  // hk_kkt_rhs only reads it
-    // the per-set arrays: base_args' sV16 / sV32 are the strides between sets
+    // the per-set arrays: batch_args' sV16 / sV32 are the strides between sets
     a.vb = b;
     a.vq = q;
     a.d = d;
@@ -51,11 +47,9 @@ extern "C" int hpmpc_mi355x_kkt_new_rhs_batch(const hpmpc_mi355x_plan* plan, con
     memset(&x, 0, sizeof x);
     x.nrhs = nrhs;
     x.scratch = scratch;
-    x.sS = kkt_scratch_doubles(P->N);
-    if (const int e = hk_kkt_rhs_launch(&a, &x, count, (hipStream_t)stream)) {
-        hk_set_error(e == HK_LAUNCH_REFUSED ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP, "hk_kkt_rhs launch failed");
-        return g_err;
-    }
+    x.sS = kkt_scratch_doubles(plan->N);
+    if (const int e = hk_kkt_rhs_launch(&a, &x, count, (hipStream_t)stream))
+        return launch_error(e, "hk_kkt_rhs launch failed");
     return g_err = 0;
 }
 

@@ -10,28 +10,23 @@
 // concatenated in stage order, column-major or row-major blocks by the plan's flag; per array a problem stride, 0
 // for data shared by every problem.  One difference from pack_problem(): RSQrq_k gets S in both triangles, as
 // oracle/iface_oracle.py to_qp builds it (pack_problem leaves the upper one zero; every kernel reads the lower).
-#include "hk_launch_guard.h"
+#include <memory>
+
 #include "hk_ocp_args.h"
 #include "hk_plan.h"
 
 struct hpmpc_mi355x_ocp_plan {
-    hpmpc_mi355x_plan* tile = nullptr;
+    std::unique_ptr<hpmpc_mi355x_plan> tile;
     int N = 0, row_major = 0;
     std::vector<OcpStage> st;
     long long dense[OCP_NARR] = {};  // doubles per problem of every dense array
     long long su = 0, sx = 0, sp = 0, sl = 0;  // u, x, pi, lam / t outputs
     long long sRes = 0;                        // hk_res output per problem
-    OcpStage* d_st = nullptr;
-    int* d_idx = nullptr;
+    DevTable<OcpStage> d_st;
+    DevTable<int> d_idx;
 };
 
-extern "C" void hpmpc_mi355x_ocp_plan_destroy(hpmpc_mi355x_ocp_plan* O) {
-    if (!O) return;
-    if (O->tile) hpmpc_mi355x_plan_destroy(O->tile);
-    if (O->d_st) (void)hipFree(O->d_st);
-    if (O->d_idx) (void)hipFree(O->d_idx);
-    delete O;
-}
+extern "C" void hpmpc_mi355x_ocp_plan_destroy(hpmpc_mi355x_ocp_plan* O) { delete O; }
 
 extern "C" hpmpc_mi355x_ocp_plan* hpmpc_mi355x_ocp_plan_create(int N, const int* nx, const int* nu, const int* nb,
                                                                const int* const* idxb, const int* ng, int row_major) {
@@ -50,15 +45,16 @@ extern "C" hpmpc_mi355x_ocp_plan* hpmpc_mi355x_ocp_plan_create(int N, const int*
     auto* O = new hpmpc_mi355x_ocp_plan();
     O->N = N;
     O->row_major = row_major ? 1 : 0;
-    O->tile = hpmpc_mi355x_plan_create(N, nx, nu, nb, idxb, ng);  // the tile path's limits
+    O->tile.reset(hpmpc_mi355x_plan_create(N, nx, nu, nb, idxb, ng));  // the tile path's limits
     if (!O->tile) {
-        hpmpc_mi355x_ocp_plan_destroy(O);
+        delete O;
         return nullptr;
     }
-    const hpmpc_mi355x_plan* P = O->tile;
+    const hpmpc_mi355x_plan* P = O->tile.get();
     const long long n1 = N + 1;
     O->st.resize(n1);
     std::vector<int> idx(n1 * 16, 0);
+    idxb_table(N, nb, idxb, idx.data());
     long long* D = O->dense;
     for (int k = 0; k <= N; k++) {
         OcpStage& s = O->st[k];
@@ -74,7 +70,6 @@ extern "C" hpmpc_mi355x_ocp_plan* hpmpc_mi355x_ocp_plan_create(int N, const int*
         const int nux = s.nu + s.nx;
         if (k < N)  // outputs(): for (j = 0; j < nb[k] && idxb[k][j] < nu[k]; j++)
             while (s.nbu < s.nb && idxb[k][s.nbu] < s.nu) s.nbu++;
-        for (int l = 0; l < s.nb; l++) idx[k * 16 + l] = idxb[k][l];
         s.sd[OCP_SEC_BABT] = h.sdB;
         s.sd[OCP_SEC_RSQ] = h.sdR;
         s.sd[OCP_SEC_DCT] = rup(s.ng, NCL);
@@ -105,12 +100,8 @@ extern "C" hpmpc_mi355x_ocp_plan* hpmpc_mi355x_ocp_plan_create(int N, const int*
     O->sp = D[OCP_b];
     O->sl = 2 * D[OCP_lb] + 2 * D[OCP_lg];
     O->sRes = 2 * n1 * V16 + 2 * n1 * V32;
-    const bool ok = hip_ok(hipMalloc((void**)&O->d_st, sizeof(OcpStage) * n1), "ocp plan alloc") &&
-                    hip_ok(hipMalloc((void**)&O->d_idx, sizeof(int) * 16 * n1), "ocp plan alloc") &&
-                    hip_ok(hipMemcpy(O->d_st, O->st.data(), sizeof(OcpStage) * n1, hipMemcpyHostToDevice), "ocp plan") &&
-                    hip_ok(hipMemcpy(O->d_idx, idx.data(), sizeof(int) * 16 * n1, hipMemcpyHostToDevice), "ocp plan");
-    if (!ok) {
-        hpmpc_mi355x_ocp_plan_destroy(O);
+    if (!O->d_st.upload(O->st, "ocp plan tables") || !O->d_idx.upload(idx, "ocp plan tables")) {
+        delete O;
         return nullptr;
     }
     g_err = 0;
@@ -118,7 +109,7 @@ extern "C" hpmpc_mi355x_ocp_plan* hpmpc_mi355x_ocp_plan_create(int N, const int*
 }
 
 extern "C" const hpmpc_mi355x_plan* hpmpc_mi355x_ocp_tile_plan(const hpmpc_mi355x_ocp_plan* O) {
-    return O ? O->tile : nullptr;
+    return O ? O->tile.get() : nullptr;
 }
 
 // out[HPMPC_MI355X_OCP_NSIZES]: doubles per problem, see include/hpmpc_mi355x.h
@@ -150,40 +141,6 @@ extern "C" int hpmpc_mi355x_ocp_offsets(const hpmpc_mi355x_ocp_plan* O, long lon
     return 0;
 }
 
-namespace {
-
-bool range_ok(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, const char* who) {
-    if (O && nprob > 0 && p0 >= 0 && count >= 0 && (long long)p0 + count <= nprob) return true;
-    char msg[128];
-    snprintf(msg, sizeof msg, "%s: plan or problem range", who);
-    hk_set_error(HPMPC_MI355X_EUNSUPPORTED, msg);
-    return false;
-}
-
-int null_array(const char* who) {
-    char msg[128];
-    snprintf(msg, sizeof msg, "%s: a required array is null", who);
-    hk_set_error(HPMPC_MI355X_EUNSUPPORTED, msg);
-    return g_err;
-}
-
-int launch_error(int e, const char* what) {
-    hk_set_error(e == HK_LAUNCH_REFUSED ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP, what);
-    return g_err;
-}
-
-// the tile plan's tables with the packed default layout and the DCt array
-KArgs packed_args(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, const double* DCt) {
-    const hpmpc_mi355x_plan* P = O->tile;
-    KArgs a = base_args(P, nprob, p0);
-    a.sB = P->packB;
-    a.sR = P->packR;
-    a.DCt = P->ngt ? DCt : nullptr;
-    return a;
-}
-
-}  // namespace
-
 extern "C" int hpmpc_mi355x_ocp_pack_batch(const hpmpc_mi355x_ocp_plan* O, const hpmpc_mi355x_ocp_data* data,
                                            int matrices, int nprob, int p0, int count, double* BAbt, double* RSQrq,
                                            double* DCt, double* d, const double* u0, const double* x0, double* ux,
@@ -211,7 +168,7 @@ extern "C" int hpmpc_mi355x_ocp_pack_batch(const hpmpc_mi355x_ocp_plan* O, const
     a.count = count;
     a.matrices = matrices ? 1 : 0;
     a.row_major = O->row_major;
-    a.st = O->d_st;
+    a.st = O->d_st.get();
     a.out[OCP_SEC_BABT] = BAbt;
     a.out[OCP_SEC_RSQ] = RSQrq;
     a.out[OCP_SEC_DCT] = DCt;
@@ -252,7 +209,8 @@ extern "C" int hpmpc_mi355x_ocp_ipm_batch(const hpmpc_mi355x_ocp_plan* O, int np
     if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !ws || !kk || !ret || (k_max > 0 && !stat) ||
         (O->tile->ngt && !DCt))
         return null_array(who);
-    KArgs a = packed_args(O, nprob, p0, DCt);
+    KArgs a;  // the tile plan's tables with the packed default layout and the DCt array
+    if (!batch_args(a, O->tile.get(), nullptr, nprob, p0, DCT_ARRAY, DCt)) return g_err;
     return ipm_run(a, count, BAbt, RSQrq, d, ux, pi, lam, t, ws, k_max, mu0, mu_tol, alpha_min, warm_start,
                    compute_mult, kk, ret, stat, K_IPM, stream);
 }
@@ -273,7 +231,8 @@ extern "C" int hpmpc_mi355x_ocp_finish_batch(const hpmpc_mi355x_ocp_plan* O, int
         return null_array(who);
     const long long n1 = O->N + 1;
     double* mu = res + (long long)nprob * O->sRes;
-    KArgs a = packed_args(O, nprob, p0, DCt);
+    KArgs a;
+    if (!batch_args(a, O->tile.get(), nullptr, nprob, p0, DCT_ARRAY, DCt)) return g_err;
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
     a.d = d;
@@ -285,15 +244,15 @@ extern "C" int hpmpc_mi355x_ocp_finish_batch(const hpmpc_mi355x_ocp_plan* O, int
     a.sW = O->sRes;
     a.res_plain = 1;  // d_res_mpc_hard_tv
     a.mu_out = mu;
-    if (hk_launch(K_RES, &a, count, (hipStream_t)stream)) return launch_error(-1, "hk_res launch failed");
+    if (const int e = hk_launch(K_RES, &a, count, (hipStream_t)stream)) return launch_error(e, "hk_res launch failed");
     OcpFinishArgs f;
     memset(&f, 0, sizeof f);
     f.N = O->N;
     f.nprob = nprob;
     f.p0 = p0;
     f.count = count;
-    f.st = O->d_st;
-    f.idxb = O->d_idx;
+    f.st = O->d_st.get();
+    f.idxb = O->d_idx.get();
     f.d = d;
     f.ux = ux;
     f.pi = pi;

@@ -322,10 +322,9 @@ extern "C" int hpmpc_mi355x_ipm_queue(const hpmpc_mi355x_plan* plan, const hpmpc
                                       int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
                                       int compute_mult, int* kk, int* ret, double* stat, double* pass_ms,
                                       int* n_ticks, void* stream) {
-    auto* P = const_cast<hpmpc_mi355x_plan*>(plan);
-    if (!P || nprob <= 0 || nq < 0 || n_slots <= 0 || !qctl) return g_err = HPMPC_MI355X_EUNSUPPORTED;
-    KArgs a = base_args(P, nprob, 0);
-    if (!layout_apply(P, lay, a)) return g_err;
+    if (!plan || nprob <= 0 || nq < 0 || n_slots <= 0 || !qctl) return g_err = HPMPC_MI355X_EUNSUPPORTED;
+    KArgs a;
+    if (!batch_args(a, plan, lay, nprob, 0, DCT_NONE)) return g_err;
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
     a.d = d;

@@ -71,6 +71,37 @@ const char* soft_layout(int N, const int* nx, const int* nu, const int* nb, cons
     return nullptr;
 }
 
+double soft_mu_scal(int N, const int* nb, const int* ns) {
+    double m = 0.0;
+    for (int k = 0; k <= N; k++) m += 2 * nb[k] + 4 * ns[k];
+    return m > 0.0 ? 1.0 / m : 0.0;
+}
+
+void soft_ric_flags(KArgs& a, int compute_mult) {
+    a.use_box = 1;
+    a.update_q = 1;
+    a.update_b = 0;
+    a.compute_pi = compute_mult;
+    a.compute_Pb = 1;
+}
+
+SoftArgs soft_scalars(int N, int nprob, int p0, int k_max, int warm_start, double mu0, double mu_tol, double alpha_min,
+                      double mu_scal) {
+    SoftArgs s;
+    memset(&s, 0, sizeof s);
+    s.N = N;
+    s.nprob = nprob;
+    s.p0 = p0;
+    s.k_max = k_max;
+    s.warm_start = warm_start;
+    s.nq = (N + 4) / 4;
+    s.mu0 = mu0;
+    s.mu_tol = mu_tol;
+    s.alpha_min = alpha_min;
+    s.mu_scal = mu_scal;
+    return s;
+}
+
 namespace {
 
 bool soft_launch(int which, const SoftArgs& s) {
@@ -105,13 +136,11 @@ extern "C" int d_ip2_mpc_soft_tv(int* kk, int k_max, double mu0, double mu_tol, 
         hk_set_error(HPMPC_MI355X_EUNSUPPORTED, why);
         return g_err;
     }
-    double mu_scal = 0.0;
-    for (int k = 0; k <= N; k++) mu_scal += 2 * nb[k] + 2 * ng[k] + 4 * ns[k];
+    const double mu_scal = soft_mu_scal(N, nb, ns);  // every ng is 0 here
     if (mu_scal == 0.0) {  // the reference solves into its workspace and leaves every output untouched (:273-284)
         *kk = 0;
         return 0;
     }
-    mu_scal = 1.0 / mu_scal;
     std::vector<int> nbs(N + 1);
     for (int k = 0; k <= N; k++) nbs[k] = nb[k] + ns[k];
     hpmpc_mi355x_plan* P = thread_plan(N, nx, nu, nbs.data(), idxb, ng);
@@ -143,11 +172,10 @@ extern "C" int d_ip2_mpc_soft_tv(int* kk, int k_max, double mu0, double mu_tol, 
     stage_BAbt(P, H, A, pBAbt);
     stage_RSQ(P, H, A, pQ);
     memcpy(H + oTab, ss.data(), sizeof(SoftStage) * n1);
-    int* hidx = reinterpret_cast<int*>(H + oIdx);
+    idxb_table(N, nbs.data(), idxb, reinterpret_cast<int*>(H + oIdx));  // the pinned arena is cleared (ensure)
     for (int k = 0; k <= N; k++) {
         const SoftStage& s = ss[k];
         const int nux = s.nu + s.nx;
-        for (int l = 0; l < nbs[k]; l++) hidx[k * 16 + l] = idxb[k][l];
         for (int l = 0; l < nux; l++) H[A.vq + k * V16 + l] = P4(pQ[k], rup(nux, NCL), nux, l);
         if (k < N) {  // b_k with the reference's stride round_up(nx_{k+1}, 4) (d_ip2_soft.c:172)
             const double* row = pBAbt[k] + (nux / BS) * BS * rup(s.nx1, BS) + nux % BS;
@@ -162,21 +190,11 @@ extern "C" int d_ip2_mpc_soft_tv(int* kk, int k_max, double mu0, double mu_tol, 
     }
     double* D = reinterpret_cast<double*>(g_dev.dev);
     KArgs a = arena_args(P, A, D);
-    a.use_box = 1;
-    a.update_q = 1;
-    a.update_b = 0;
-    a.compute_pi = compute_mult;
-    a.compute_Pb = 1;
+    soft_ric_flags(a, compute_mult);
     KArgs a2 = a;
     a2.compute_Pb = 0;
-    SoftArgs s;
-    memset(&s, 0, sizeof s);
-    s.N = N;
-    s.nprob = 1;
-    s.k_max = k_max;
-    s.warm_start = warm_start;
-    s.nq = (N + 4) / 4;
-    s.st = reinterpret_cast<const SoftStage*>(D + oTab);
+    SoftArgs s = soft_scalars(N, 1, 0, k_max, warm_start, mu0, mu_tol, alpha_min, mu_scal);
+    s.st =reinterpret_cast<const SoftStage*>(D + oTab);
     s.idxb = reinterpret_cast<const int*>(D + oIdx);
     s.d = D + oD;
     s.Z = D + oZ;
@@ -194,10 +212,6 @@ extern "C" int d_ip2_mpc_soft_tv(int* kk, int k_max, double mu0, double mu_tol, 
     s.dpi = D + A.pi;
     s.vQx = D + A.vQx;
     s.vqx = D + A.vqx;
-    s.mu0 = mu0;
-    s.mu_tol = mu_tol;
-    s.alpha_min = alpha_min;
-    s.mu_scal = mu_scal;
     s.scal = D + oScal;
     s.ist = reinterpret_cast<int*>(D + oIst);
     s.stat = D + oStat;

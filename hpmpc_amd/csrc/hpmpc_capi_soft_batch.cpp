@@ -8,27 +8,22 @@
 // layouts at the offsets of hpmpc_mi355x_soft_offsets, ux / pi with 16 doubles per stage, and a workspace:
 //   [ factor (N+1) FSTRIDE | dux dpi b q Qx qx Pb, (N+1) 16 each | dt dlam lamt tinv | flat Qx qx Zl zl | scal | ist ]
 // (the flat block in the reference's carve order with its padding, hk_soft_args.h).
-#include "hk_launch_guard.h"
+#include <memory>
+
 #include "hk_plan.h"
 
 struct hpmpc_mi355x_soft_plan {
-    hpmpc_mi355x_plan* tile = nullptr;
+    std::unique_ptr<hpmpc_mi355x_plan> tile;
     int N = 0;
     SoftLayout L;
-    double mu_scal = 0.0;  // 1 / sum(2 nb + 4 ns); 0: no constraint anywhere
+    double mu_scal = 0.0;  // soft_mu_scal; 0: no constraint anywhere
     // workspace carve (doubles)
     long long oV16 = 0, oCv = 0, nCv = 0, oFlat = 0, oScal = 0, oIst = 0, ws = 0;
-    SoftStage* d_st = nullptr;
-    int* d_idx = nullptr;
+    DevTable<SoftStage> d_st;
+    DevTable<int> d_idx;
 };
 
-extern "C" void hpmpc_mi355x_soft_plan_destroy(hpmpc_mi355x_soft_plan* S) {
-    if (!S) return;
-    if (S->tile) hpmpc_mi355x_plan_destroy(S->tile);
-    if (S->d_st) (void)hipFree(S->d_st);
-    if (S->d_idx) (void)hipFree(S->d_idx);
-    delete S;
-}
+extern "C" void hpmpc_mi355x_soft_plan_destroy(hpmpc_mi355x_soft_plan* S) { delete S; }
 
 extern "C" hpmpc_mi355x_soft_plan* hpmpc_mi355x_soft_plan_create(int N, const int* nx, const int* nu, const int* nb,
                                                                  const int* const* idxb, const int* ng,
@@ -48,19 +43,18 @@ extern "C" hpmpc_mi355x_soft_plan* hpmpc_mi355x_soft_plan_create(int N, const in
     }
     auto* S = new hpmpc_mi355x_soft_plan();
     S->N = N;
-    S->tile = hpmpc_mi355x_plan_create(N, nx, nu, nbs.data(), idxb, ng);  // tile limits, round_up(nb + ns, 4) <= 16
+    // the tile path's limits, round_up(nb + ns, 4) <= 16 among them
+    S->tile.reset(hpmpc_mi355x_plan_create(N, nx, nu, nbs.data(), idxb, ng));
     if (!S->tile) {
-        hpmpc_mi355x_soft_plan_destroy(S);
+        delete S;
         return nullptr;
     }
     if (const char* why = soft_layout(N, nx, nu, nb, ns, S->L)) {
         hk_set_error(HPMPC_MI355X_EUNSUPPORTED, why);
-        hpmpc_mi355x_soft_plan_destroy(S);
+        delete S;
         return nullptr;
     }
-    double m = 0.0;
-    for (int k = 0; k <= N; k++) m += 2 * nb[k] + 4 * ns[k];
-    S->mu_scal = m > 0.0 ? 1.0 / m : 0.0;
+    S->mu_scal = soft_mu_scal(N, nb, ns);
     const long long n1 = N + 1;
     auto r8 = [](long long n) { return (n + 7) / 8 * 8; };
     long long o = n1 * FSTRIDE;
@@ -77,15 +71,9 @@ extern "C" hpmpc_mi355x_soft_plan* hpmpc_mi355x_soft_plan_create(int N, const in
     o += 8;
     S->ws = (o + 31) / 32 * 32;  // 256-byte granules: every problem's arrays keep their cache-line alignment
     std::vector<int> idx(n1 * 16, 0);
-    for (int k = 0; k <= N; k++)
-        for (int l = 0; l < nbs[k]; l++) idx[k * 16 + l] = idxb[k][l];
-    const bool ok = hip_ok(hipMalloc((void**)&S->d_st, sizeof(SoftStage) * n1), "soft plan alloc") &&
-                    hip_ok(hipMalloc((void**)&S->d_idx, sizeof(int) * 16 * n1), "soft plan alloc") &&
-                    hip_ok(hipMemcpy(S->d_st, S->L.st.data(), sizeof(SoftStage) * n1, hipMemcpyHostToDevice),
-                           "soft plan") &&
-                    hip_ok(hipMemcpy(S->d_idx, idx.data(), sizeof(int) * 16 * n1, hipMemcpyHostToDevice), "soft plan");
-    if (!ok) {
-        hpmpc_mi355x_soft_plan_destroy(S);
+    idxb_table(N, nbs.data(), idxb, idx.data());
+    if (!S->d_st.upload(S->L.st, "soft plan tables") || !S->d_idx.upload(idx, "soft plan tables")) {
+        delete S;
         return nullptr;
     }
     g_err = 0;
@@ -113,7 +101,7 @@ extern "C" int hpmpc_mi355x_soft_offsets(const hpmpc_mi355x_soft_plan* S, long l
 }
 
 // d_ip2_mpc_soft_tv on problems [p0, p0 + count) of a device-resident batch.  Asynchronous on `stream`: two launches
-// (hk_soft_ipm_init, hk_soft_ipm), no synchronisation (a layout's first use uploads its stage table, layout_apply).
+// (hk_soft_ipm_init, hk_soft_ipm), no synchronisation (a layout's first use uploads its stage table, batch_args).
 extern "C" int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan* S, const hpmpc_mi355x_layout* lay, int nprob,
                                            int p0, int count, const double* BAbt, const double* RSQrq,
                                            const double* Z, const double* z, const double* d, double* ux, double* pi,
@@ -121,8 +109,10 @@ extern "C" int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan* S, cons
                                            double alpha_min, int warm_start, int compute_mult, int* kk, int* ret,
                                            double* stat, void* stream) {
     g_err = 0;
-    if (!S || nprob <= 0 || p0 < 0 || count < 0 || p0 + count > nprob || k_max < 0 || !kk || !ret) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ipm_soft_batch: plan, problem range or k_max");
+    const char* who = "hpmpc_mi355x_ipm_soft_batch";
+    if (!range_ok(S, nprob, p0, count, who)) return g_err;
+    if (k_max < 0 || !kk || !ret) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ipm_soft_batch: k_max >= 0, kk and ret are required");
         return g_err;
     }
     if (count == 0) return 0;
@@ -136,15 +126,12 @@ extern "C" int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan* S, cons
         return 0;
     }
     const bool soft = S->L.sZ > 0;
-    if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !ws || (k_max > 0 && !stat) || (soft && (!Z || !z))) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ipm_soft_batch: a required array is null");
-        return g_err;
-    }
-    hpmpc_mi355x_plan* P = S->tile;
+    if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !ws || (k_max > 0 && !stat) || (soft && (!Z || !z)))
+        return null_array(who);
     const int N = S->N;
     const long long n1 = N + 1, v16 = n1 * V16;
-    KArgs a = base_args(P, nprob, p0);
-    if (!layout_apply(P, lay, a)) return g_err;
+    KArgs a;
+    if (!batch_args(a, S->tile.get(), lay, nprob, p0, DCT_NONE)) return g_err;
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
     a.ws = ws;
@@ -158,22 +145,11 @@ extern "C" int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan* S, cons
     a.vQx = V + 4 * v16;
     a.vqx = V + 5 * v16;
     a.vPb = V + 6 * v16;
-    a.use_box = 1;
-    a.update_q = 1;
-    a.update_b = 0;
-    a.compute_pi = compute_mult;
-    a.compute_Pb = 1;
+    soft_ric_flags(a, compute_mult);
     a.k_max = k_max;
-    SoftArgs s;
-    memset(&s, 0, sizeof s);
-    s.N = N;
-    s.nprob = nprob;
-    s.p0 = p0;
-    s.k_max = k_max;
-    s.warm_start = warm_start;
-    s.nq = (N + 4) / 4;
-    s.st = S->d_st;
-    s.idxb = S->d_idx;
+    SoftArgs s = soft_scalars(N, nprob, p0, k_max, warm_start, mu0, mu_tol, alpha_min, S->mu_scal);
+    s.st = S->d_st.get();
+    s.idxb = S->d_idx.get();
     s.d = d;
     s.Z = Z;
     s.z = z;
@@ -200,18 +176,10 @@ extern "C" int hpmpc_mi355x_ipm_soft_batch(const hpmpc_mi355x_soft_plan* S, cons
     s.scal = ws + S->oScal;
     s.ist = reinterpret_cast<int*>(ws + S->oIst);
     s.sW = S->ws;
-    s.mu0 = mu0;
-    s.mu_tol = mu_tol;
-    s.alpha_min = alpha_min;
-    s.mu_scal = S->mu_scal;
     s.stat = stat;
     s.sS = 5LL * k_max;
     s.kk = kk;
     s.ret = ret;
-    if (const int e = hk_soft_ipm_launch(&a, &s, count, st)) {
-        hk_set_error(e == HK_LAUNCH_REFUSED ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP,
-                     "hk_soft_ipm launch failed");
-        return g_err;
-    }
+    if (const int e = hk_soft_ipm_launch(&a, &s, count, st)) return launch_error(e, "hk_soft_ipm launch failed");
     return g_err = 0;
 }

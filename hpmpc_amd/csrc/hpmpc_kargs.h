@@ -7,6 +7,10 @@
 constexpr int FSTRIDE = 352;  // factor doubles per stage: 4 regs x 64 lanes + l (16) + inv_diag (16) + KG (64)
 constexpr int V16 = 16;       // per-stage stride of tile/state vectors
 constexpr int V32 = 32;       // per-stage stride of constraint vectors ([lb | pad | ub | pad])
+// LDS bytes of the tile kernels' stage tables (lds_table_bytes, hk_ipm_body.h, which ties them to the structs): the
+// kernel's Scratch, then per stage StageInfo + tile / slot tables + the certificate bound
+constexpr int LDS_FIXED = 256;
+constexpr int LDS_PER_STAGE = 104;
 
 // Launch ids of hk_launch (hpmpc_kernels.hip launch_t), and K_SV of the ric2 variant's hk_launch_ric2.
 enum HkLaunch {

@@ -366,11 +366,6 @@ __device__ __forceinline__ bool update_body_mw(const KArgs& a, const IpmView& v0
     return ipm_continue<FX, CI, MW_WAVES>(a, v, kk, mu, alpha, sigma, phase, mws);
 }
 
-// LDS of the multi-wave kernel: the stage tables (lds_tables, dynamic) beside the static hk_mw object
-__host__ __device__ constexpr size_t mw_lds_bytes(int N) {
-    return sizeof(Scratch) + (size_t)(N + 1) * (sizeof(StageInfo) + 40);
-}
-
 }  // namespace
 
 // The multi-wave solve of one problem (its workspace, iterate and data: who), from the loop-control state its
@@ -587,7 +582,8 @@ __global__ __launch_bounds__(64) void hk_kkt_new_rhs_p1(KArgs a) {
 template <class FX>
 static int launch_t(int which, const KArgs* a, int count, hipStream_t stream) {
     dim3 grid(count), block(64);
-    const size_t lds = sizeof(Scratch) + (size_t)(a->N + 1) * (sizeof(StageInfo) + 40);
+    // the multi-wave kernels keep the same stage tables (lds_tables, dynamic) beside their static hk_mw object
+    const size_t lds = lds_table_bytes(a->N);
     switch (which) {
         case K_SV: hipLaunchKernelGGL(hk_ric_sv<FX>, grid, block, lds, stream, *a); break;
         case K_TRF: hipLaunchKernelGGL(hk_ric_trf<FX>, grid, block, lds, stream, *a); break;
@@ -622,10 +618,9 @@ static int launch_t(int which, const KArgs* a, int count, hipStream_t stream) {
             static const HkKernelLimits lim_mw(reinterpret_cast<const void*>(&hk_ipm_solo_mw<FX>));
             const char* env = getenv("HPMPC_MI355X_SOLO");
             const bool single = which == K_SOLO_1W || (env && env[0] == '1');
-            const size_t lds_mw = mw_lds_bytes(a->N);
             hipLaunchKernelGGL(hk_ipm_init<FX>, grid, block, lds, stream, *a);
-            if (!single && a->N <= MW_NMAX && lim_mw.check(lds_mw, 256) == 0)
-                hipLaunchKernelGGL(hk_ipm_solo_mw<FX>, grid, dim3(256), lds_mw, stream, *a);
+            if (!single && a->N <= MW_NMAX && lim_mw.check(lds, 256) == 0)
+                hipLaunchKernelGGL(hk_ipm_solo_mw<FX>, grid, dim3(256), lds, stream, *a);
             else
                 hipLaunchKernelGGL(hk_ipm_solo<FX>, grid, block, lds, stream, *a);
             break;
@@ -634,9 +629,8 @@ static int launch_t(int which, const KArgs* a, int count, hipStream_t stream) {
         // horizon or the launch guard rules the multi-wave kernel out (the host then keeps ticking)
         case K_QDRAIN: {
             static const HkKernelLimits lim_dr(reinterpret_cast<const void*>(&hk_ipm_qdrain_mw<FX>));
-            const size_t lds_mw = mw_lds_bytes(a->N);
-            if (a->N > MW_NMAX || lim_dr.check(lds_mw, 256) != 0) return HK_LAUNCH_REFUSED;
-            hipLaunchKernelGGL(hk_ipm_qdrain_mw<FX>, grid, dim3(256), lds_mw, stream, *a);
+            if (a->N > MW_NMAX || lim_dr.check(lds, 256) != 0) return HK_LAUNCH_REFUSED;
+            hipLaunchKernelGGL(hk_ipm_qdrain_mw<FX>, grid, dim3(256), lds, stream, *a);
             break;
         }
         default: return -1;
@@ -644,13 +638,7 @@ static int launch_t(int which, const KArgs* a, int count, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-// Compiled inner-stage classes (KArgs.fixcls): 0 generic, 1 nu=4 nx=12, 2 nu=3 nx=8.  The plan picks
-// the class and flags its stages (StageInfo.r0); any other problem runs the generic kernels.
-extern "C" int hk_fixcls(int nu, int nx) {
-    if (nu == 4 && nx == 12) return 1;
-    if (nu == 3 && nx == 8) return 2;
-    return 0;
-}
+extern "C" int hk_fixcls(int nu, int nx) { return fixcls_of(nu, nx); }
 
 #ifdef HK_STAMPS
 // Diagnostic build only: the clamp-certificate counters of the tile kernels (g_xfac_stat), read and optionally reset.
@@ -679,9 +667,7 @@ extern "C" int hk_launch(int which, const KArgs* a, int count, hipStream_t strea
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_mw_fault), &fault, sizeof(fault));
     }
 #endif
-    switch (a->fixcls) {
-        case 1: return launch_t<FixSh<4, 12>>(which, a, count, stream);
-        case 2: return launch_t<FixSh<3, 8>>(which, a, count, stream);
-        default: return launch_t<NoFix>(which, a, count, stream);
-    }
+    return with_fixcls(a->fixcls, [&](auto fx) {
+        return launch_t<typename decltype(fx)::type>(which, a, count, stream);
+    });
 }

@@ -22,6 +22,8 @@ import ctypes as C
 
 import numpy as np
 
+from .bindings import check, lib, plan_args
+
 KEYS = ("A", "B", "b", "Q", "S", "R", "q", "r", "lb", "ub", "C", "D", "lg", "ug")  # HkOcpArray / hpmpc_mi355x_ocp_data
 OUT_KEYS = ("u", "x", "pi", "lam", "t")
 NSIZES, NOFFSETS = 29, 18  # HPMPC_MI355X_OCP_NSIZES / _NOFFSETS
@@ -135,49 +137,16 @@ class _OcpData(C.Structure):
     _fields_ = [("ptr", C.c_void_p * len(KEYS)), ("stride", C.c_longlong * len(KEYS))]
 
 
-_READY = False
-
-
-def ocp_lib():
-    """The library with the argument types of the hpmpc_mi355x_ocp_* calls declared."""
-    global _READY
-    from .batch import lib
-
-    L = lib()
-    if not _READY:
-        vp, i, d = C.c_void_p, C.c_int, C.c_double
-        L.hpmpc_mi355x_ocp_plan_create.restype = vp
-        L.hpmpc_mi355x_ocp_plan_create.argtypes = [i, vp, vp, vp, vp, vp, i]
-        L.hpmpc_mi355x_ocp_plan_destroy.argtypes = [vp]
-        L.hpmpc_mi355x_ocp_tile_plan.restype = vp
-        L.hpmpc_mi355x_ocp_tile_plan.argtypes = [vp]
-        L.hpmpc_mi355x_ocp_sizes.argtypes = [vp, vp]
-        L.hpmpc_mi355x_ocp_offsets.argtypes = [vp, vp]
-        L.hpmpc_mi355x_ocp_pack_batch.restype = i
-        L.hpmpc_mi355x_ocp_pack_batch.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.hpmpc_mi355x_ocp_ipm_batch.restype = i
-        L.hpmpc_mi355x_ocp_ipm_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d, i, i, vp,
-                                                 vp, vp, vp]
-        L.hpmpc_mi355x_ocp_finish_batch.restype = i
-        L.hpmpc_mi355x_ocp_finish_batch.argtypes = [vp, i, i, i] + [vp] * 16
-        if hasattr(L, "hpmpc_mi355x_ocp_kkt_batch"):  # absent from an A/B library of before it (HPMPC_MI355X_LIB)
-            L.hpmpc_mi355x_ocp_kkt_batch.restype = i
-            L.hpmpc_mi355x_ocp_kkt_batch.argtypes = [vp, i, i, i] + [vp] * 11
-        _READY = True
-    return L
+ocp_lib = lib  # the hpmpc_mi355x_ocp_* calls are bound with every other one (hpmpc_amd.bindings)
 
 
 def ocp_plan_create(N, nx, nu, nb, idxb, ng, order="C"):
     """(plan handle or None, error code, keep-alive objects) of hpmpc_mi355x_ocp_plan_create."""
-    L = ocp_lib()
-    ints = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    L = lib()
     nuv = list(nu) + [0] * (N + 1 - len(nu))
-    arrs = [ints(nx), ints(nuv), ints(nb), ints(ng)]
-    idx = [np.ascontiguousarray(i, dtype=np.int32) for i in idxb]
-    idxp = (C.POINTER(C.c_int) * (N + 1))(*[a.ctypes.data_as(C.POINTER(C.c_int)) for a in idx])
-    plan = L.hpmpc_mi355x_ocp_plan_create(N, arrs[0].ctypes.data, arrs[1].ctypes.data, arrs[2].ctypes.data,
-                                          C.cast(idxp, C.c_void_p), arrs[3].ctypes.data, 1 if order == "C" else 0)
-    return (plan or None), L.hpmpc_mi355x_last_error(), (arrs, idx, idxp)
+    (pnx, pnu, pnb, png), idxp, keep = plan_args(idxb, nx, nuv, nb, ng)
+    plan = L.hpmpc_mi355x_ocp_plan_create(N, pnx, pnu, pnb, idxp, png, 1 if order == "C" else 0)
+    return (plan or None), L.hpmpc_mi355x_last_error(), keep
 
 
 class OcpBatchSolver:
@@ -198,7 +167,7 @@ class OcpBatchSolver:
         self.nx, self.nu = [int(v) for v in nx], [int(v) for v in nu][:N] + [0]
         self.nb, self.ng = [int(v) for v in nb], [int(v) for v in ng]
         self.dev = torch.device(device)
-        L = ocp_lib()
+        L = lib()
         self.plan, err, self._keep = ocp_plan_create(N, self.nx, self.nu, self.nb, idxb, self.ng, order)
         if not self.plan:
             raise ValueError(f"unsupported problem sizes for the batched OCP front end (code {err})")
@@ -226,7 +195,7 @@ class OcpBatchSolver:
     def __del__(self):
         try:
             if getattr(self, "plan", None):
-                ocp_lib().hpmpc_mi355x_ocp_plan_destroy(self.plan)
+                lib().hpmpc_mi355x_ocp_plan_destroy(self.plan)
         except Exception:
             pass
 
@@ -273,23 +242,20 @@ class OcpBatchSolver:
             if (su, sx) != (self.sizes["u"], self.sizes["x"]) and self.nprob > 1:
                 raise ValueError("warm u / x: contiguous (nprob, size) tensors expected")
             ux = self.ux.data_ptr()
-        rc = ocp_lib().hpmpc_mi355x_ocp_pack_batch(
+        check(lib().hpmpc_mi355x_ocp_pack_batch(
             self.plan, C.byref(ds), 1 if matrices else 0, self.nprob, p0, count, self.BAbt.data_ptr(),
             self.RSQrq.data_ptr(), self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), u0, x0, ux,
-            self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ocp_pack_batch failed ({rc})")
+            self._stream()), "hpmpc_mi355x_ocp_pack_batch")
 
     def solve(self, mu0=2.0, mu_tol=1e-10, alpha_min=1e-8, warm_start=0, p0=0, count=None):
         """d_ip2_res_mpc_hard_tv on the packed batch (mu0 > 0: one value for the batch)."""
         p0, count = self._range(p0, count)
-        rc = ocp_lib().hpmpc_mi355x_ocp_ipm_batch(
+        check(lib().hpmpc_mi355x_ocp_ipm_batch(
             self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
             self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
             self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(), self.k_max, mu0, mu_tol,
-            alpha_min, warm_start, 1, self.kk.data_ptr(), self.ret.data_ptr(), self.stat.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ocp_ipm_batch failed ({rc})")
+            alpha_min, warm_start, 1, self.kk.data_ptr(), self.ret.data_ptr(), self.stat.data_ptr(),
+            self._stream()), "hpmpc_mi355x_ocp_ipm_batch")
 
     def kkt_buffers(self, nrhs: int = 1) -> dict:
         """The output and scratch tensors kkt_sets(nrhs=nrhs) writes (allocated on first use, then reused);
@@ -300,7 +266,7 @@ class OcpBatchSolver:
             raise ValueError("nrhs >= 1 expected")
         bufs = self.__dict__.setdefault("_kkt", {})
         if nrhs not in bufs:
-            bufs[nrhs] = kkt_buffers(self.torch, self.dev, ocp_lib().hpmpc_mi355x_ocp_tile_plan(self.plan), self.N,
+            bufs[nrhs] = kkt_buffers(self.torch, self.dev, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), self.N,
                                      self.nprob, nrhs)
         return bufs[nrhs]
 
@@ -312,13 +278,11 @@ class OcpBatchSolver:
         resolve() may be called again with other data.  Needs a solve() with at least one iteration."""
         p0, count = self._range(p0, count)
         self.pack(data, matrices=False, p0=p0, count=count)
-        rc = ocp_lib().hpmpc_mi355x_ocp_kkt_batch(
+        check(lib().hpmpc_mi355x_ocp_kkt_batch(
             self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
             self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
             self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(),
-            self.kkt_buffers(1)["scratch"].data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ocp_kkt_batch failed ({rc})")
+            self.kkt_buffers(1)["scratch"].data_ptr(), self._stream()), "hpmpc_mi355x_ocp_kkt_batch")
 
     def kkt_sets(self, b, q, d, nrhs=1, p0=0, count=None, compute_mult=1):
         """hpmpc_mi355x_kkt_new_rhs_batch with the tile plan on the packed arrays: ``nrhs`` right-hand-side sets per
@@ -330,25 +294,21 @@ class OcpBatchSolver:
 
         p0, count = self._range(p0, count)
         out = self.kkt_buffers(nrhs)
-        rc = kkt_sets_call(self.torch, ocp_lib().hpmpc_mi355x_ocp_tile_plan(self.plan), None, self.N, self.nprob, p0,
-                           count, nrhs, self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None, b, q, d, out,
-                           self.ws, compute_mult, self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_kkt_new_rhs_batch failed ({rc})")
+        check(kkt_sets_call(self.torch, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), None, self.N, self.nprob, p0,
+                            count, nrhs, self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None, b, q, d, out,
+                            self.ws, compute_mult, self._stream()), "hpmpc_mi355x_kkt_new_rhs_batch")
         return out["ux"], out["pi"], out["lam"], out["t"]
 
     def finish(self, p0=0, count=None) -> dict:
         """The wrappers' outputs as device tensors (nprob, size): u, x (equality-box fix applied), pi, compact lam
         and t, inf_norm_res (nprob, 4), kk and status per problem.  Asynchronous: synchronise before reading."""
         p0, count = self._range(p0, count)
-        rc = ocp_lib().hpmpc_mi355x_ocp_finish_batch(
+        check(lib().hpmpc_mi355x_ocp_finish_batch(
             self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
             self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
             self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.res.data_ptr(), self.u.data_ptr(),
             self.x.data_ptr(), self.pi_out.data_ptr(), self.lam_out.data_ptr(), self.t_out.data_ptr(),
-            self.inf_norm_res.data_ptr(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ocp_finish_batch failed ({rc})")
+            self.inf_norm_res.data_ptr(), self._stream()), "hpmpc_mi355x_ocp_finish_batch")
         s = self.sizes
         return dict(u=self.u[:, :s["u"]], x=self.x[:, :s["x"]], pi=self.pi_out[:, :s["pi_out"]],
                     lam=self.lam_out[:, :s["lam_out"]], t=self.t_out[:, :s["lam_out"]],

@@ -19,40 +19,8 @@ import ctypes as C
 
 import numpy as np
 
-from .batch import lib
+from .bindings import lib, plan_args
 from .ocp import OCPQP
-
-_BOUND = False
-
-
-def _bind():
-    global _BOUND
-    L = lib()
-    if _BOUND:
-        return L
-    vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
-    L.hpmpc_mi355x_pcond_plan_create.restype = vp
-    L.hpmpc_mi355x_pcond_plan_create.argtypes = [i, vp, vp, vp, vp, vp, i]
-    L.hpmpc_mi355x_pcond_plan_destroy.argtypes = [vp]
-    L.hpmpc_mi355x_pcond_sizes.argtypes = [vp, vp]
-    L.hpmpc_mi355x_pcond_offsets.argtypes = [vp, i, vp]
-    L.hpmpc_mi355x_pcond_batch.restype = i
-    L.hpmpc_mi355x_pcond_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.hpmpc_mi355x_pcond_ric_sv_batch.restype = i
-    L.hpmpc_mi355x_pcond_ric_sv_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, i, vp]
-    L.hpmpc_mi355x_pexpand_batch.restype = i
-    L.hpmpc_mi355x_pexpand_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.hpmpc_mi355x_pcond_wide_plan.restype = vp
-    L.hpmpc_mi355x_pcond_wide_plan.argtypes = [vp]
-    L.hpmpc_mi355x_wide_sizes.argtypes = [vp, vp]
-    L.hpmpc_mi355x_wide_offsets.argtypes = [vp, vp]
-    L.hpmpc_mi355x_wide_ipm_batch.restype = i
-    d = C.c_double
-    L.hpmpc_mi355x_wide_ipm_batch.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d, i, i, vp,
-                                              vp, vp, vp]
-    _ = ll
-    _BOUND = True
-    return L
 
 
 class PcondSolver:
@@ -68,15 +36,10 @@ class PcondSolver:
         self.qp = qp
         self.N, self.N2, self.nprob = qp.N, N2, qp.batch
         self.dev = torch.device(device)
-        L = _bind()
+        L = lib()
         N = qp.N
-        idx = [np.ascontiguousarray(i, dtype=np.int32) for i in qp.idxb]
-        idxp = (C.POINTER(C.c_int) * (N + 1))(*[a.ctypes.data_as(C.POINTER(C.c_int)) for a in idx])
-        ints = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        self._keep = [idx, idxp]
-        nx, nu, nb, ng = ints(qp.nx), ints(qp.nu), ints(qp.nb), ints(qp.ng)
-        self.plan = L.hpmpc_mi355x_pcond_plan_create(N, nx.ctypes.data, nu.ctypes.data, nb.ctypes.data,
-                                                     C.cast(idxp, C.c_void_p), ng.ctypes.data, N2)
+        (nx, nu, nb, ng), idxp, self._keep = plan_args(qp.idxb, qp.nx, qp.nu, qp.nb, qp.ng)
+        self.plan = L.hpmpc_mi355x_pcond_plan_create(N, nx, nu, nb, idxp, ng, N2)
         if not self.plan:
             raise ValueError(f"unsupported partial condensing (code {L.hpmpc_mi355x_last_error()})")
         sz = (C.c_longlong * 15)()
@@ -116,7 +79,7 @@ class PcondSolver:
     def __del__(self):
         try:
             if getattr(self, "plan", None):
-                _bind().hpmpc_mi355x_pcond_plan_destroy(self.plan)
+                lib().hpmpc_mi355x_pcond_plan_destroy(self.plan)
         except Exception:
             pass
 
@@ -134,21 +97,21 @@ class PcondSolver:
     def condense(self, p0=0, count=None):
         count = self.nprob - p0 if count is None else count
         p = self._p
-        self._check(_bind().hpmpc_mi355x_pcond_batch(self.plan, self.nprob, p0, count, p(self.BAbt), p(self.RSQrq),
+        self._check(lib().hpmpc_mi355x_pcond_batch(self.plan, self.nprob, p0, count, p(self.BAbt), p(self.RSQrq),
                                                      p(self.d), p(self.G), p(self.BAbt2), p(self.RSQrq2),
                                                      p(self.DCt2), p(self.d2), self._stream()), "pcond")
 
     def riccati(self, p0=0, count=None, compute_pi=1):
         count = self.nprob - p0 if count is None else count
         p = self._p
-        self._check(_bind().hpmpc_mi355x_pcond_ric_sv_batch(self.plan, self.nprob, p0, count, p(self.BAbt2),
+        self._check(lib().hpmpc_mi355x_pcond_ric_sv_batch(self.plan, self.nprob, p0, count, p(self.BAbt2),
                                                             p(self.RSQrq2), p(self.ws2), p(self.ux2), p(self.pi2),
                                                             compute_pi, self._stream()), "condensed sv")
 
     def expand(self, p0=0, count=None):
         count = self.nprob - p0 if count is None else count
         p = self._p
-        self._check(_bind().hpmpc_mi355x_pexpand_batch(self.plan, self.nprob, p0, count, p(self.BAbt), p(self.RSQrq),
+        self._check(lib().hpmpc_mi355x_pexpand_batch(self.plan, self.nprob, p0, count, p(self.BAbt), p(self.RSQrq),
                                                        p(self.ux2), p(self.pi2), p(self.lam2), p(self.t2), p(self.ux),
                                                        p(self.pi), p(self.lam), p(self.t), self._stream()), "expand")
 
@@ -161,7 +124,7 @@ class PcondSolver:
     def ipm(self, k_max=50, mu0=2.0, mu_tol=1e-12, alpha_min=1e-8, p0=0, count=None):
         """d_ip2_res_mpc_hard_tv on the condensed problems (hpmpc_mi355x_wide_ipm_batch, the wide-stage IPM: one
         workgroup per problem, one launch): ux2 / pi2 / lam2 / t2, and kk2 / ret2 / stat2 per problem."""
-        L = _bind()
+        L = lib()
         torch = self.torch
         if not getattr(self, "wplan", None):
             self.wplan = L.hpmpc_mi355x_pcond_wide_plan(self.plan)

@@ -13,6 +13,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from .bindings import check, lib, plan_args
 from .ocp import mass_spring_dynamics, pack_lib4_batch, rup
 
 
@@ -247,40 +248,14 @@ def unpack_soft_solution(template: SoftQP, ux, pi, lam, t, kk, ret, stat) -> lis
     return out
 
 
-def _soft_lib():
-    import ctypes as C
-
-    from .batch import lib
-
-    L = lib()
-    if not getattr(L, "_soft_bound", False):
-        vp, i, d = C.c_void_p, C.c_int, C.c_double
-        L.hpmpc_mi355x_soft_plan_create.restype = vp
-        L.hpmpc_mi355x_soft_plan_create.argtypes = [i, vp, vp, vp, vp, vp, vp]
-        L.hpmpc_mi355x_soft_plan_destroy.argtypes = [vp]
-        L.hpmpc_mi355x_soft_sizes.restype = i
-        L.hpmpc_mi355x_soft_sizes.argtypes = [vp, vp]
-        L.hpmpc_mi355x_soft_offsets.restype = i
-        L.hpmpc_mi355x_soft_offsets.argtypes = [vp, vp]
-        L.hpmpc_mi355x_ipm_soft_batch.restype = i
-        L.hpmpc_mi355x_ipm_soft_batch.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, d, d, d,
-                                                  i, i, vp, vp, vp, vp]
-        L._soft_bound = True
-    return L
+_soft_lib = lib  # the soft calls are bound with every other one (hpmpc_amd.bindings)
 
 
 def soft_plan_create(sq: SoftQP):
     """hpmpc_mi355x_soft_plan_create on a SoftQP's sizes.  Returns (plan or None, last error code)."""
-    import ctypes as C
-
-    L = _soft_lib()
-    N = sq.N
-    iv = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    nx, nu, nb, ng, ns = iv(sq.nx), iv(sq.nu), iv(sq.nb), iv(sq.ng), iv(sq.ns)
-    idx = [iv(a) for a in sq.idxb]
-    idxp = (C.POINTER(C.c_int) * (N + 1))(*[a.ctypes.data_as(C.POINTER(C.c_int)) for a in idx])
-    plan = L.hpmpc_mi355x_soft_plan_create(N, nx.ctypes.data, nu.ctypes.data, nb.ctypes.data,
-                                           C.cast(idxp, C.c_void_p), ng.ctypes.data, ns.ctypes.data)
+    L = lib()
+    (nx, nu, nb, ng, ns), idxp, _keep = plan_args(sq.idxb, sq.nx, sq.nu, sq.nb, sq.ng, sq.ns)
+    plan = L.hpmpc_mi355x_soft_plan_create(sq.N, nx, nu, nb, idxp, ng, ns)
     return (plan or None), int(L.hpmpc_mi355x_last_error())
 
 
@@ -305,7 +280,7 @@ class SoftBatchSolver:
         self.template = t = self.sqs[0]
         self.N, self.nprob, self.k_max = t.N, len(self.sqs), int(k_max)
         self.dev = torch.device(device)
-        L = _soft_lib()
+        L = lib()
         pk = pack_soft_batch(self.sqs)
         self.plan, err = soft_plan_create(t)
         if not self.plan:
@@ -351,7 +326,7 @@ class SoftBatchSolver:
     def __del__(self):
         try:
             if getattr(self, "plan", None):
-                _soft_lib().hpmpc_mi355x_soft_plan_destroy(self.plan)
+                lib().hpmpc_mi355x_soft_plan_destroy(self.plan)
         except Exception:
             pass
 
@@ -376,14 +351,12 @@ class SoftBatchSolver:
         # stat keeps the stride the call uses: 5 k_max per problem
         stat = self.stat if k_max == self.k_max else self.stat.view(-1)[:self.nprob * 5 * max(k_max, 1)]
         self._stat_kmax = k_max
-        rc = _soft_lib().hpmpc_mi355x_ipm_soft_batch(
+        check(lib().hpmpc_mi355x_ipm_soft_batch(
             self.plan, C.byref(self.layout), self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
             self.Z.data_ptr(), self.z.data_ptr(), self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(),
             self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(), k_max, mu0, mu_tol, alpha_min, warm_start,
             compute_mult, self.kk.data_ptr(), self.ret.data_ptr(), stat.data_ptr(),
-            self.torch.cuda.current_stream(self.dev).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"hpmpc_mi355x_ipm_soft_batch failed ({rc})")
+            self.torch.cuda.current_stream(self.dev).cuda_stream), "hpmpc_mi355x_ipm_soft_batch")
 
     def results(self) -> list:
         """Synchronise and return the per-problem dicts of unpack_soft_solution."""

@@ -17,6 +17,7 @@ CASES = {
     "V0": (5, [0, 3, 3, 5, 5, 4], [2, 2, 1, 3, 3], 2, 2, None),  # the same without general constraints
     "F": (4, [0, 8, 8, 8, 8], [3, 3, 3, 3], 3, 4, None),         # inner stages of the compiled (3, 8) class
     "S": (1, [2, 2], [1], 1, 1, None),                           # smallest horizon
+    "R": (2, [2, 2, 2], [1, 1], 1, 0, None),                     # one box per stage: the shape of the refusal tests
 }
 ARGS = dict(mu0=2.0, mu_tol=1e-10, alpha_min=1e-8)
 K_MAX = 50

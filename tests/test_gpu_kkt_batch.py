@@ -351,3 +351,35 @@ def test_refusals_and_the_empty_call(refs):
         assert np.array_equal(_bits(h), _bits(np.full_like(h, SENTINEL)))
     with pytest.raises(ValueError):
         sv.kkt_sets(b, q, d, nrhs=2)  # the arrays hold one set per problem
+
+
+def test_range_and_null_refusals():
+    """hpmpc_mi355x_kkt_new_rhs_batch on the smallest shape (N = 2, nx = 2, nu = 1, one box, two problems): p0 < 0,
+    p0 + count > nprob (also where p0 + count or nprob * nrhs passes INT_MAX) and a null required array return
+    HPMPC_MI355X_EUNSUPPORTED and leave it in hpmpc_mi355x_last_error(); count == 0 returns 0 with last_error 0;
+    nothing is written."""
+    Ps = problems("R", (1, 2))
+    sv = make_solver(Ps, "C", k_max=5)
+    L = ocp_lib()
+    tile = L.hpmpc_mi355x_ocp_tile_plan(sv.plan)
+    b, q, d = (sv.torch.from_numpy(x.reshape(2, 1, sv.N + 1, -1)).to(sv.dev) for x in kkt_set_arrays(Ps))
+    bufs = sv.kkt_buffers(1)
+    outs = [bufs[n] for n in ("ux", "pi", "lam", "t", "scratch")]
+    for x in outs:
+        x.fill_(SENTINEL)
+    p = lambda x, given=True: x.data_ptr() if given else None
+
+    def core(p0, count, ok=True, nrhs=1):
+        return L.hpmpc_mi355x_kkt_new_rhs_batch(tile, None, sv.nprob, p0, count, nrhs, p(sv.BAbt), p(sv.RSQrq), None,
+                                                p(b), p(q), p(d), p(outs[0], ok), p(outs[1]), p(outs[2]), p(outs[3]),
+                                                p(sv.ws), p(outs[4]), 1, sv._stream())
+
+    for args in ((-1, 1), (1, 2), (0, 3), (2, 1), (2 ** 31 - 1, 1), (0, 2, False), (0, 2, True, 2 ** 30)):
+        assert core(*args) == EUNSUPPORTED, args
+        assert L.hpmpc_mi355x_last_error() == EUNSUPPORTED, args
+    for args in ((0, 0), (2, 0), (0, 0, False)):  # an empty range asks for no array
+        assert core(*args) == 0, args
+        assert L.hpmpc_mi355x_last_error() == 0, args
+    sv.torch.cuda.synchronize()
+    for x in outs:
+        assert bool((x == SENTINEL).all())

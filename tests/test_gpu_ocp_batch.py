@@ -228,6 +228,51 @@ def test_refusals_and_the_empty_call(refs):
     assert plan is None and err == EUNSUPPORTED
 
 
+def test_range_and_null_refusals_of_every_call():
+    """hpmpc_mi355x_ocp_pack_batch, _ocp_ipm_batch and _ocp_finish_batch each: p0 < 0, p0 + count > nprob (also where
+    p0 + count passes INT_MAX) and a null required array return HPMPC_MI355X_EUNSUPPORTED and leave it in
+    hpmpc_mi355x_last_error(); count == 0 returns 0 with last_error 0; none of them writes anything."""
+    L = ocp_lib()
+    Ps = problems("R", (1, 2))
+    sv = make_solver(Ps, "C", k_max=5)
+    state = (sv.BAbt, sv.RSQrq, sv.d, sv.ux, sv.pi, sv.lam, sv.t, sv.ws, sv.stat, sv.u, sv.x, sv.pi_out, sv.lam_out,
+             sv.t_out, sv.inf_norm_res, sv.res)
+    for x in state:
+        x.fill_(SENTINEL)
+    sv.kk.fill_(-3)
+    sv.ret.fill_(-3)
+    sv.torch.cuda.synchronize()
+    ds = sv.data_struct(to_device(sv, flatten_problems(Ps, "C")))
+    p = lambda x, given=True: x.data_ptr() if given else None
+
+    def pack(p0, count, ok=True):
+        return L.hpmpc_mi355x_ocp_pack_batch(sv.plan, C.byref(ds), 1, sv.nprob, p0, count, p(sv.BAbt), p(sv.RSQrq, ok),
+                                             None, p(sv.d), None, None, None, sv._stream())
+
+    def ipm(p0, count, ok=True):
+        return L.hpmpc_mi355x_ocp_ipm_batch(sv.plan, sv.nprob, p0, count, p(sv.BAbt), p(sv.RSQrq), None, p(sv.d),
+                                            p(sv.ux), p(sv.pi), p(sv.lam), p(sv.t), p(sv.ws, ok), sv.k_max, 2.0, 1e-10,
+                                            1e-8, 0, 1, p(sv.kk), p(sv.ret), p(sv.stat), sv._stream())
+
+    def finish(p0, count, ok=True):
+        return L.hpmpc_mi355x_ocp_finish_batch(sv.plan, sv.nprob, p0, count, p(sv.BAbt), p(sv.RSQrq), None, p(sv.d),
+                                               p(sv.ux), p(sv.pi), p(sv.lam), p(sv.t), p(sv.res), p(sv.u), p(sv.x),
+                                               p(sv.pi_out), p(sv.lam_out), p(sv.t_out), p(sv.inf_norm_res, ok),
+                                               sv._stream())
+
+    for call in (pack, ipm, finish):
+        for args in ((-1, 1), (1, 2), (0, 3), (2, 1), (2 ** 31 - 1, 1), (0, 2, False)):
+            assert call(*args) == EUNSUPPORTED, (call.__name__, args)
+            assert L.hpmpc_mi355x_last_error() == EUNSUPPORTED, (call.__name__, args)
+        for args in ((0, 0), (2, 0), (0, 0, False)):  # an empty range asks for no array
+            assert call(*args) == 0, (call.__name__, args)
+            assert L.hpmpc_mi355x_last_error() == 0, (call.__name__, args)
+    sv.torch.cuda.synchronize()
+    for x in state:
+        assert bool((x == SENTINEL).all())
+    assert sv.kk.tolist() == [-3, -3] and sv.ret.tolist() == [-3, -3]
+
+
 def test_sizes_and_offsets_match_the_host_layout(refs):
     for case in ("V", "F"):
         P = problems(case, [1])[0]

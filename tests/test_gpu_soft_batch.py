@@ -169,6 +169,39 @@ def test_refusals():
     assert plan is None and err == EUNSUPPORTED
 
 
+def test_range_and_null_refusals():
+    """hpmpc_mi355x_ipm_soft_batch on the smallest shape (N = 2, nx = 2, nu = 1, one box per stage, two problems):
+    p0 < 0, p0 + count > nprob and a null required array return HPMPC_MI355X_EUNSUPPORTED and leave it in
+    hpmpc_mi355x_last_error(); count == 0 returns 0 with last_error 0; nothing is written."""
+    from hpmpc_amd.soft import _soft_lib
+
+    sv = SoftBatchSolver([mass_spring_soft(N=2, nx=2, nu=1, soft=False)] * 2, k_max=5)
+    L = _soft_lib()
+    outs = (sv.ux, sv.pi, sv.lam, sv.t, sv.ws, sv.stat)
+    for x in outs:
+        x.fill_(-7.25)
+    sv.kk.fill_(-3)
+    sv.ret.fill_(-3)
+    p = lambda x, given=True: x.data_ptr() if given else None
+
+    def call(p0, count, ok=True):
+        return L.hpmpc_mi355x_ipm_soft_batch(sv.plan, None, sv.nprob, p0, count, p(sv.BAbt), p(sv.RSQrq), None, None,
+                                             p(sv.d), p(sv.ux), p(sv.pi), p(sv.lam, ok), p(sv.t), p(sv.ws), 5, 100.0,
+                                             1e-6, 1e-8, 0, 1, p(sv.kk), p(sv.ret), p(sv.stat),
+                                             sv.torch.cuda.current_stream(sv.dev).cuda_stream)
+
+    for args in ((-1, 1), (1, 2), (0, 3), (2, 1), (0, 2, False)):
+        assert call(*args) == EUNSUPPORTED, args
+        assert L.hpmpc_mi355x_last_error() == EUNSUPPORTED, args
+    for args in ((0, 0), (2, 0), (0, 0, False)):  # an empty range asks for no array
+        assert call(*args) == 0, args
+        assert L.hpmpc_mi355x_last_error() == 0, args
+    sv.torch.cuda.synchronize()
+    for x in outs:
+        assert bool((x == -7.25).all())
+    assert sv.kk.tolist() == [-3, -3] and sv.ret.tolist() == [-3, -3]
+
+
 def test_no_constraints_leaves_outputs():
     sqs = [mass_spring_soft(N=5, nx=4, nu=2, soft=False, hard=False)] * 2
     sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
