@@ -138,6 +138,26 @@ def kkt_sets_call(torch, plan, layout, N, nprob, p0, count, nrhs, BAbt, RSQrq, D
         ptr(out["pi"]), ptr(out["lam"]), ptr(out["t"]), ptr(ws), ptr(out["scratch"]), compute_mult, stream)
 
 
+def kkt_tangent_call(torch, plan, layout, N, nprob, p0, count, ndir, BAbt, RSQrq, DCt, db, dq, dd, out, ws,
+                     compute_mult, stream) -> int:
+    """hpmpc_mi355x_kkt_tangent_batch on torch tensors, after checking the shapes of the per-set arrays: db, dq
+    (nprob, ndir, N+1, 16), dd (nprob, ndir, N+1, 32), each or all None (a zero direction); ``out`` from
+    kkt_buffers(ndir), whose ux / pi / lam / t receive dux / dpi / dlam / dt.  Returns the library's code."""
+    for name, x, w in (("db", db, 16), ("dq", dq, 16), ("dd", dd, 32)):
+        if x is None:
+            continue
+        if tuple(x.shape) != (nprob, ndir, N + 1, w) or x.dtype != torch.float64 or not x.is_contiguous():
+            raise ValueError(f"{name}: contiguous float64 tensor of shape {(nprob, ndir, N + 1, w)} expected")
+    for name, w in (("ux", 16), ("pi", 16), ("lam", 32), ("t", 32)):
+        if tuple(out[name].shape) != (nprob, ndir, N + 1, w):
+            raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={ndir}) expected")
+    ptr = lambda x: None if x is None else x.data_ptr()
+    return lib().hpmpc_mi355x_kkt_tangent_batch(
+        plan, layout, nprob, p0, count, ndir, ptr(BAbt), ptr(RSQrq), ptr(DCt), ptr(db), ptr(dq), ptr(dd),
+        ptr(out["ux"]), ptr(out["pi"]), ptr(out["lam"]), ptr(out["t"]), ptr(ws), ptr(out["scratch"]), compute_mult,
+        stream)
+
+
 class BatchSolver:
     """Device-resident batch of OCP QPs + the batched HPMPC entry points.
 
@@ -254,6 +274,20 @@ class BatchSolver:
         check(kkt_sets_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, nrhs, self.BAbt,
                             self.RSQrq, None, b, q, d, out, self.ws, compute_mult, self._stream()),
               "hpmpc_mi355x_kkt_new_rhs_batch")
+        return out["ux"], out["pi"], out["lam"], out["t"]
+
+    def kkt_tangent(self, db, dq, dd, ndir=1, p0=0, count=None, compute_mult=1, out=None):
+        """Batched KKT tangent solve (hpmpc_mi355x_kkt_tangent_batch): the directional derivative of kkt_new_rhs's
+        result with respect to (b, q, d), ``ndir`` direction sets per problem in one launch, on the factor ipm() /
+        ipm_solo() left.  db, dq: (nprob, ndir, N+1, 16), dd: (nprob, ndir, N+1, 32), or None for a zero direction.
+        Returns dux, dpi, dlam, dt with a leading (nprob, ndir) shape: the tensors of ``out`` (default: those of
+        kkt_buffers(ndir), which the next kkt_new_rhs / kkt_tangent call of that set count overwrites).  ws and the
+        problem data are not written.  Asynchronous on torch's current stream."""
+        count = self.nprob - p0 if count is None else count
+        out = self.kkt_buffers(ndir) if out is None else out
+        check(kkt_tangent_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, ndir,
+                               self.BAbt, self.RSQrq, None, db, dq, dd, out, self.ws, compute_mult, self._stream()),
+              "hpmpc_mi355x_kkt_tangent_batch")
         return out["ux"], out["pi"], out["lam"], out["t"]
 
     def ipm_pass(self, pss, *, mu0=2.0, mu_tol=1e-12, alpha_min=1e-8, warm_start=0, compute_mult=1, p0=0,

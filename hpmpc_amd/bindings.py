@@ -60,6 +60,9 @@ _SIG = dict(
     kkt_scratch_doubles="l:p",
     kkt_new_rhs_batch="i:ppiiiippppppppppppip",
     ocp_kkt_batch="i:piiippppppppppp",
+    ocp_unpack_sets="i:piiiippppppppppp",
+    kkt_tangent_batch="i:ppiiiippppppppppppip",
+    ocp_tangent_batch="i:ppiiiippppppppppip",
 )
 # {function name: (restype, argtypes)}
 SIGNATURES = {"hpmpc_mi355x_" + n: (_CTYPE[s[0]], [_CTYPE[c] for c in s[2:]]) for n, s in _SIG.items()}

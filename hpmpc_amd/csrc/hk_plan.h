@@ -3,7 +3,8 @@
 // functions and call checks below), hpmpc_capi_queue.cpp (the problem queue), hpmpc_capi_dropin.cpp (reference-named
 // hard-constraint entry points; defines the arena functions), hpmpc_capi_soft.cpp (soft-constraint IPM and residual;
 // defines the soft refusals, layout and IPM setup), hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM),
-// hpmpc_capi_ocp.cpp (the batched OCP front end) and hpmpc_capi_kkt.cpp (the batched KKT re-solve).
+// hpmpc_capi_ocp.cpp (the batched OCP front end), hpmpc_capi_kkt.cpp (the batched KKT re-solve) and
+// hpmpc_capi_tan.cpp (its tangent solve and the multi-set finish; through hk_ocp_plan.h).
 #pragma once
 #include <mutex>
 #include <vector>

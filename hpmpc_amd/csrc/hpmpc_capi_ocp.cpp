@@ -10,21 +10,7 @@
 // concatenated in stage order, column-major or row-major blocks by the plan's flag; per array a problem stride, 0
 // for data shared by every problem.  One difference from pack_problem(): RSQrq_k gets S in both triangles, as
 // oracle/iface_oracle.py to_qp builds it (pack_problem leaves the upper one zero; every kernel reads the lower).
-#include <memory>
-
-#include "hk_ocp_args.h"
-#include "hk_plan.h"
-
-struct hpmpc_mi355x_ocp_plan {
-    std::unique_ptr<hpmpc_mi355x_plan> tile;
-    int N = 0, row_major = 0;
-    std::vector<OcpStage> st;
-    long long dense[OCP_NARR] = {};  // doubles per problem of every dense array
-    long long su = 0, sx = 0, sp = 0, sl = 0;  // u, x, pi, lam / t outputs
-    long long sRes = 0;                        // hk_res output per problem
-    DevTable<OcpStage> d_st;
-    DevTable<int> d_idx;
-};
+#include "hk_ocp_plan.h"
 
 extern "C" void hpmpc_mi355x_ocp_plan_destroy(hpmpc_mi355x_ocp_plan* O) { delete O; }
 

@@ -133,6 +133,41 @@ def kkt_set_arrays(problems):
     return b, q, d
 
 
+VEC_KEYS = ("b", "q", "r", "lb", "ub", "lg", "ug")  # the dense arrays a tangent direction may have
+
+
+def tangent_set_arrays(problem_deltas):
+    """The direction twin of kkt_set_arrays: interface-form DELTAS (dicts with N, nx, nu, nb, ng and any of b, q, r,
+    lb, ub, lg, ug as per-stage lists; a missing key is a zero direction) -> db (n, N+1, 16) in state order, dq
+    (n, N+1, 16) in variable order [dr_k | dq_k], dd (n, N+1, 32) as [dlb pnb | dub pnb | dlg png | dug png], padding
+    zero -- the arrays of hpmpc_mi355x_kkt_tangent_batch.  The placement is kkt_set_arrays' own, so for deltas that
+    are exactly representable kkt_set_arrays(P + delta) - kkt_set_arrays(P) equals the result bit for bit."""
+    N, nx, nu, nb, ng = _sizes_of(problem_deltas[0])
+    full = []
+    for D in problem_deltas:
+        Z = dict(D)
+        for key in VEC_KEYS:
+            if Z.get(key) is None:
+                nblk = N if key in ("b", "r") else N + 1
+                Z[key] = [np.zeros(_shape(key, N, nx, nu, nb, ng, k)) for k in range(nblk)]
+        full.append(Z)
+    return kkt_set_arrays(full)
+
+
+def x0_directions(A0, S0=None):
+    """The nx0 parameter directions of an initial state x_0 that is folded into stage 0 (nx[0] = 0, b_0 = A_0 x_0 + b,
+    r_0 = r + S_0 x_0): direction i is db_0 = A_0[:, i] and, with S0, dr_0 = S_0[:, i].  A0: (..., nx[1], nx0), S0:
+    (..., nu[0], nx0), numpy arrays or torch tensors with any leading batch shape.  Returns the stage-0 blocks
+    {"b": (..., nx0, nx[1]), "r": (..., nx0, nu[0])} (no "r" without S0); every other stage's direction is zero.
+    OcpBatchSolver.feedback_gain embeds them into the (nprob, ndir, size) tensors of tangent()."""
+    out = {"b": A0.swapaxes(-1, -2)}
+    if S0 is not None:
+        if S0.shape[-1] != A0.shape[-1]:
+            raise ValueError("A0 and S0 have one column per component of x_0")
+        out["r"] = S0.swapaxes(-1, -2)
+    return out
+
+
 class _OcpData(C.Structure):
     _fields_ = [("ptr", C.c_void_p * len(KEYS)), ("stride", C.c_longlong * len(KEYS))]
 
@@ -152,7 +187,7 @@ def ocp_plan_create(N, nx, nu, nb, idxb, ng, order="C"):
 class OcpBatchSolver:
     """``nprob`` OCPs with the given stage sizes: owns the lib4 arrays, the iterate, the workspaces and the outputs
     (torch tensors on ``device``).  pack() -> solve() -> finish(), then any number of resolve() -> finish() or
-    kkt_sets() on the factor solve() left, all asynchronous on torch's current stream.
+    kkt_sets() / tangent() on the factor solve() left, all asynchronous on torch's current stream.
     There is no CPU fallback: without a GPU or the built library the constructor raises."""
 
     def __init__(self, N, nx, nu, nb, idxb, ng, nprob, order="C", device="cuda", k_max=50):
@@ -284,12 +319,16 @@ class OcpBatchSolver:
             self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(),
             self.kkt_buffers(1)["scratch"].data_ptr(), self._stream()), "hpmpc_mi355x_ocp_kkt_batch")
 
-    def kkt_sets(self, b, q, d, nrhs=1, p0=0, count=None, compute_mult=1):
+    def kkt_sets(self, b, q, d, nrhs=1, p0=0, count=None, compute_mult=1, dense=False):
         """hpmpc_mi355x_kkt_new_rhs_batch with the tile plan on the packed arrays: ``nrhs`` right-hand-side sets per
         problem against the factor of solve().  b, q: (nprob, nrhs, N+1, 16) device tensors or None (the rows
         packed into BAbt / RSQrq); d: (nprob, nrhs, N+1, 32) (kkt_set_arrays builds all three).  Returns ux, pi,
         lam, t with a leading (nprob, nrhs) shape in the padded layouts of the iterate -- the tensors of
-        kkt_buffers(nrhs).  Neither ws nor the solver's iterate is written."""
+        kkt_buffers(nrhs).  Neither ws nor the solver's iterate is written.
+        dense=True: the sets are then unpacked on the device (hpmpc_mi355x_ocp_unpack_sets, the equality-box fix
+        from each set's own d) and the call returns the dict u, x, pi, lam, t of (nprob, nrhs, size) tensors --
+        those of set_buffers(nrhs); per set what resolve() -> finish() gives on that set's data, without the
+        residual norms."""
         from .batch import kkt_sets_call
 
         p0, count = self._range(p0, count)
@@ -297,7 +336,101 @@ class OcpBatchSolver:
         check(kkt_sets_call(self.torch, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), None, self.N, self.nprob, p0,
                             count, nrhs, self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None, b, q, d, out,
                             self.ws, compute_mult, self._stream()), "hpmpc_mi355x_kkt_new_rhs_batch")
+        if not dense:
+            return out["ux"], out["pi"], out["lam"], out["t"]
+        o = self.set_buffers(nrhs)
+        check(lib().hpmpc_mi355x_ocp_unpack_sets(
+            self.plan, self.nprob, p0, count, nrhs, d.data_ptr(), out["ux"].data_ptr(), out["pi"].data_ptr(),
+            out["lam"].data_ptr(), out["t"].data_ptr(), o["u"].data_ptr(), o["x"].data_ptr(), o["pi"].data_ptr(),
+            o["lam"].data_ptr(), o["t"].data_ptr(), self._stream()), "hpmpc_mi355x_ocp_unpack_sets")
+        return self._sized(o)
+
+    def set_buffers(self, nsets: int = 1) -> dict:
+        """The dense per-set tensors u, x, pi, lam, t of shape (nprob, nsets, max(size, 1)) that tangent(ndir=nsets)
+        and kkt_sets(nrhs=nsets, dense=True) write (allocated on first use, then reused and overwritten)."""
+        if nsets < 1:
+            raise ValueError("at least one set per problem expected")
+        bufs = self.__dict__.setdefault("_sets", {})
+        if nsets not in bufs:
+            s = self.sizes
+            new = lambda n: self.torch.zeros((self.nprob, nsets, max(n, 1)), dtype=self.torch.float64, device=self.dev)
+            bufs[nsets] = dict(u=new(s["u"]), x=new(s["x"]), pi=new(s["pi_out"]), lam=new(s["lam_out"]),
+                               t=new(s["lam_out"]))
+        return bufs[nsets]
+
+    def _sized(self, o):
+        s = self.sizes
+        return dict(u=o["u"][:, :, :s["u"]], x=o["x"][:, :, :s["x"]], pi=o["pi"][:, :, :s["pi_out"]],
+                    lam=o["lam"][:, :, :s["lam_out"]], t=o["t"][:, :, :s["lam_out"]])
+
+    def tangent(self, dirs, ndir, p0=0, count=None, compute_mult=1):
+        """Forward sensitivities of the re-solved plan (hpmpc_mi355x_ocp_tangent_batch): the directional derivative
+        of what resolve() computes with respect to its b, q, r and bounds, ``ndir`` directions per problem in one
+        launch on the factor of solve().  ``dirs``: {key: contiguous float64 device tensor (nprob, ndir,
+        sizes[key])} for any of b, q, r, lb, ub, lg, ug; a missing (or None) key is a zero direction.  A matrix key
+        is passed on and refused by the library: directions in A, B, Q, S, R, C, D are out of scope.  Returns the dict
+        u, x, pi, lam, t of (nprob, ndir, size) tensors (du, dx, dpi, compact dlam, dt) -- those of
+        set_buffers(ndir).  The equality-box fix of finish() is not applied to tangents.  compute_mult=0: pi comes
+        back as zeros.  Neither ws nor the solver's data or iterate is written."""
+        torch = self.torch
+        p0, count = self._range(p0, count)
+        ds = _OcpData()
+        for i, key in enumerate(KEYS):
+            x = dirs.get(key)
+            if x is None:
+                ds.ptr[i], ds.stride[i] = None, 0
+                continue
+            n = self.sizes[key]
+            if x.dtype != torch.float64 or x.device.type != self.dev.type or not x.is_contiguous() or \
+                    (key in VEC_KEYS and tuple(x.shape) != (self.nprob, ndir, n)):
+                raise ValueError(f"direction {key}: contiguous float64 tensor ({self.nprob}, {ndir}, {n}) on "
+                                 f"{self.dev} expected")
+            ds.ptr[i], ds.stride[i] = x.data_ptr(), n
+        o = self.set_buffers(ndir)
+        check(lib().hpmpc_mi355x_ocp_tangent_batch(
+            self.plan, C.byref(ds), self.nprob, p0, count, ndir, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
+            self.DCt.data_ptr() if self.sizes["DCt"] else None, o["u"].data_ptr(), o["x"].data_ptr(),
+            o["pi"].data_ptr(), o["lam"].data_ptr(), o["t"].data_ptr(), self.ws.data_ptr(),
+            self.kkt_buffers(ndir)["scratch"].data_ptr(), compute_mult, self._stream()),
+            "hpmpc_mi355x_ocp_tangent_batch")
+        return self._sized(o)
+
+    def tangent_sets(self, db, dq, dd, ndir=1, p0=0, count=None, compute_mult=1):
+        """The padded core of tangent() (hpmpc_mi355x_kkt_tangent_batch with the tile plan on the packed arrays): db,
+        dq (nprob, ndir, N+1, 16), dd (nprob, ndir, N+1, 32) device tensors (tangent_set_arrays builds them) or None
+        for a zero direction.  Returns dux, dpi, dlam, dt with a leading (nprob, ndir) shape in the padded layouts of
+        the iterate -- the ux, pi, lam, t tensors of kkt_buffers(ndir), which kkt_sets(nrhs=ndir) also writes."""
+        from .batch import kkt_tangent_call
+
+        p0, count = self._range(p0, count)
+        out = self.kkt_buffers(ndir)
+        check(kkt_tangent_call(self.torch, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), None, self.N, self.nprob, p0,
+                               count, ndir, self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None, db, dq, dd,
+                               out, self.ws, compute_mult, self._stream()), "hpmpc_mi355x_kkt_tangent_batch")
         return out["ux"], out["pi"], out["lam"], out["t"]
+
+    def feedback_gain(self, A0, S0=None, p0=0, count=None):
+        """d u_0 / d x_0, (nprob, nu[0], nx0), of a batch whose x_0 is folded into stage 0 (nx[0] = 0, b_0 = A_0 x_0 +
+        b, r_0 = r + S_0 x_0): one tangent() with the nx0 directions of x0_directions(A0, S0).  A0: (nprob, nx[1],
+        nx0) or (nx[1], nx0) for every problem, S0 likewise (nu[0], nx0) or None; numpy arrays or device tensors."""
+        torch = self.torch
+        if self.nx[0] != 0:
+            raise ValueError("feedback_gain: x_0 is folded into stage 0 (nx[0] = 0)")
+        dev = lambda M: None if M is None else torch.as_tensor(M, dtype=torch.float64).to(self.dev)
+        blocks = x0_directions(dev(A0), dev(S0))
+        nx0 = blocks["b"].shape[-2]
+        dirs = {}
+        for key, width in (("b", self.nx[1]), ("r", self.nu[0])):
+            if key not in blocks:
+                continue
+            blk = blocks[key]
+            if tuple(blk.shape[-2:]) != (nx0, width):
+                raise ValueError(f"feedback_gain: the stage-0 block of {key} has {width} rows")
+            full = torch.zeros((self.nprob, nx0, self.sizes[key]), dtype=torch.float64, device=self.dev)
+            full[:, :, :width] = blk  # stage 0's block starts every problem's array; a 2-D block is shared
+            dirs[key] = full
+        du = self.tangent(dirs, nx0, p0=p0, count=count)["u"]
+        return du[:, :, :self.nu[0]].transpose(1, 2)
 
     def finish(self, p0=0, count=None) -> dict:
         """The wrappers' outputs as device tensors (nprob, size): u, x (equality-box fix applied), pi, compact lam

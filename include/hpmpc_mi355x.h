@@ -598,6 +598,61 @@ int hpmpc_mi355x_kkt_new_rhs_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi
 int hpmpc_mi355x_ocp_kkt_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, int p0, int count, const double *BAbt,
                                const double *RSQrq, const double *DCt, const double *d, double *ux, double *pi,
                                double *lam, double *t, const double *ws, double *scratch, void *stream);
+/* The multi-set finish: the padded ux, pi, lam, t and d of nprob * nrhs re-solved sets (the arrays of
+ * hpmpc_mi355x_kkt_new_rhs_batch) -> per set u, x, pi_out shaped like r, q, b and lam_out, t_out compact as
+ * [lb nb | ub nb | lg ng | ug ng], all (nprob, nrhs, size) with the per-problem sizes hpmpc_mi355x_ocp_sizes reports
+ * at [23..26].  The equality-box fix of hpmpc_mi355x_ocp_finish_batch is applied from the set's own d (the same loop
+ * bound and comparison).  Pure data movement, one launch; t_out may be null.  The residual norms per set
+ * (inf_norm_res) are out of scope: they need the set's b / q / d in a residual pass per set, which this call does
+ * not run.  nrhs < 1, a bad range or a null required pointer return HPMPC_MI355X_EUNSUPPORTED and write nothing. */
+int hpmpc_mi355x_ocp_unpack_sets(const hpmpc_mi355x_ocp_plan *plan, int nprob, int p0, int count, int nrhs,
+                                 const double *d, const double *ux, const double *pi, const double *lam,
+                                 const double *t, double *u, double *x, double *pi_out, double *lam_out,
+                                 double *t_out, void *stream);
+
+/* ---- the KKT tangent solve: forward sensitivities of the re-solve, one set per parameter direction ----
+ * The re-solve above is an affine map of (b, q, d): the factor is fixed, the step length is 1 and there is no line
+ * search.  This call computes its linear part T directly,
+ *   T(db, dq, dd) = kkt(b + db, q + dq, d + dd) - kkt(b, q, d)   in exact arithmetic, for any base (b, q, d),
+ * with no base solve and no subtraction: one Riccati solve on the persisted factor per direction, without the
+ * re-solve's residual pass and backup copies.  Result: (dux, dpi, dlam, dt), the directional derivative of the
+ * re-solved (ux, pi, lam, t) -- e.g. d u_0 / d x_0 for a problem whose x_0 is folded into b_0 and r_0 (the feedback
+ * gain of a sensitivity-based or advanced-step MPC update), or the sensitivity of the plan to a bound.  It is exactly
+ * linear: the zero direction gives zeros and a direction scaled by a power of two gives the scaled result bit for bit.
+ * Every problem takes ndir direction sets; set s = p * ndir + r belongs to problem p.  One launch, one wavefront per
+ * set.  Layouts and conventions are the re-solve's: db 16 doubles per stage in state order, dq 16 doubles per stage
+ * in variable order [dr_k | dq_k], dd 32 doubles per stage as [dlb | dub | dlg | dug], nprob * ndir sets of each; the
+ * results likewise (dux, dpi 16, dlam, dt 32 doubles per stage; every element of the sets in range is written,
+ * padding as zeros).  Any of db, dq, dd may be null: a zero direction (all three null give zero results).
+ * Which ws is valid: exactly what is valid for hpmpc_mi355x_kkt_new_rhs_batch (an IPM of the same problems with
+ * kk >= 1; not a queue solve).  Of it the call reads the factor, t^-1 and the multiplier backup; it never writes ws
+ * (nor BAbt, RSQrq, DCt, the directions), so tangents and re-solves may follow one IPM in any number and order.
+ * Takes tile plans with ng > 0 and layouts like the re-solve.  scratch: nprob * ndir *
+ * hpmpc_mi355x_kkt_scratch_doubles(plan) doubles, no initialisation needed and no result depends on its contents.
+ * compute_mult = 0: dpi is returned as zeros.  Asynchronous on `stream`, synchronises with nothing; only the sets of
+ * problems [p0, p0+count) are read or written; count = 0 returns 0.  ndir < 1, a bad range, a null required pointer,
+ * a null DCt with ng > 0 or a refused launch return HPMPC_MI355X_EUNSUPPORTED and write nothing.
+ * Out of scope, refused or absent rather than half-built: reverse mode (adjoint solves), directions in the matrices
+ * (A, B, Q, S, R, C, D), and per-set residual norms. */
+int hpmpc_mi355x_kkt_tangent_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi355x_layout *lay, int nprob, int p0,
+                                   int count, int ndir, const double *BAbt, const double *RSQrq, const double *DCt,
+                                   const double *db, const double *dq, const double *dd, double *dux, double *dpi,
+                                   double *dlam, double *dt, const double *ws, double *scratch, int compute_mult,
+                                   void *stream);
+/* The same for dense directions and dense results on an OCP plan (packed default layout).  dirs: only the vector
+ * entries b, q, r, lb, ub, lg, ug are read; stride[i] is the number of doubles between consecutive SETS (nprob * ndir
+ * of them, problem-major), a null pointer is a zero direction, and a non-null matrix entry (A, B, Q, S, R, C, D) is
+ * refused with HPMPC_MI355X_EUNSUPPORTED.  Results per set: du shaped like r, dx like q, dpi like b, dlam / dt compact
+ * as [lb nb | ub nb | lg ng | ug ng]; all (nprob, ndir, size) with the per-problem sizes of hpmpc_mi355x_ocp_sizes
+ * [23..26].  The equality-box fix of hpmpc_mi355x_ocp_finish_batch is NOT applied to tangents: the fix overwrites
+ * u with the bound where lb == ub, a property of the base point; the tangent of such an input is what the Newton
+ * system gives (zero up to the rounding of 1 / t), not the bound's direction.  Seeding and unpacking are the
+ * prologue and epilogue of the one kernel launch: no host copy, no synchronisation, no padded array of the caller's.
+ * scratch as above. */
+int hpmpc_mi355x_ocp_tangent_batch(const hpmpc_mi355x_ocp_plan *plan, const hpmpc_mi355x_ocp_data *dirs, int nprob,
+                                   int p0, int count, int ndir, const double *BAbt, const double *RSQrq,
+                                   const double *DCt, double *du, double *dx, double *dpi, double *dlam, double *dt,
+                                   const double *ws, double *scratch, int compute_mult, void *stream);
 
 #ifdef __cplusplus
 }
