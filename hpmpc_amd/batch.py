@@ -119,23 +119,32 @@ def kkt_buffers(torch, dev, plan, N: int, nprob: int, nrhs: int) -> dict:
                 scratch=new(int(lib().hpmpc_mi355x_kkt_scratch_doubles(plan))))
 
 
+def _set_call(fn, names, optional, torch, plan, layout, N, nprob, p0, count, nsets, BAbt, RSQrq, DCt, vecs, out, ws,
+              compute_mult, stream) -> int:
+    """A call with the argument list of hpmpc_mi355x_kkt_new_rhs_batch on torch tensors, after checking the shapes of
+    the per-set arrays ``vecs`` (V16, V16, V32 per stage, called ``names``; None allowed for those in ``optional``) and
+    of ``out`` from kkt_buffers(nsets).  Returns the library's code."""
+    for name, x, w in zip(names, vecs, (16, 16, 32)):
+        if x is None and name in optional:
+            continue
+        if x is None or tuple(x.shape) != (nprob, nsets, N + 1, w) or x.dtype != torch.float64 or not x.is_contiguous():
+            raise ValueError(f"{name}: contiguous float64 tensor of shape {(nprob, nsets, N + 1, w)} expected")
+    for name, w in (("ux", 16), ("pi", 16), ("lam", 32), ("t", 32)):
+        if tuple(out[name].shape) != (nprob, nsets, N + 1, w):
+            raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={nsets}) expected")
+    ptr = lambda x: None if x is None else x.data_ptr()
+    return fn(plan, layout, nprob, p0, count, nsets, ptr(BAbt), ptr(RSQrq), ptr(DCt), *(ptr(x) for x in vecs),
+              ptr(out["ux"]), ptr(out["pi"]), ptr(out["lam"]), ptr(out["t"]), ptr(ws), ptr(out["scratch"]), compute_mult,
+              stream)
+
+
 def kkt_sets_call(torch, plan, layout, N, nprob, p0, count, nrhs, BAbt, RSQrq, DCt, b, q, d, out, ws, compute_mult,
                   stream) -> int:
     """hpmpc_mi355x_kkt_new_rhs_batch on torch tensors, after checking the shapes of the per-set arrays: b, q (nprob,
     nrhs, N+1, 16) or None (the problem's augmented rows), d (nprob, nrhs, N+1, 32), ``out`` from kkt_buffers.
     Returns the library's code."""
-    for name, x, w in (("b", b, 16), ("q", q, 16), ("d", d, 32)):
-        if x is None and name != "d":
-            continue
-        if x is None or tuple(x.shape) != (nprob, nrhs, N + 1, w) or x.dtype != torch.float64 or not x.is_contiguous():
-            raise ValueError(f"{name}: contiguous float64 tensor of shape {(nprob, nrhs, N + 1, w)} expected")
-    for name, w in (("ux", 16), ("pi", 16), ("lam", 32), ("t", 32)):
-        if tuple(out[name].shape) != (nprob, nrhs, N + 1, w):
-            raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={nrhs}) expected")
-    ptr = lambda x: None if x is None else x.data_ptr()
-    return lib().hpmpc_mi355x_kkt_new_rhs_batch(
-        plan, layout, nprob, p0, count, nrhs, ptr(BAbt), ptr(RSQrq), ptr(DCt), ptr(b), ptr(q), ptr(d), ptr(out["ux"]),
-        ptr(out["pi"]), ptr(out["lam"]), ptr(out["t"]), ptr(ws), ptr(out["scratch"]), compute_mult, stream)
+    return _set_call(lib().hpmpc_mi355x_kkt_new_rhs_batch, ("b", "q", "d"), ("b", "q"), torch, plan, layout, N, nprob,
+                     p0, count, nrhs, BAbt, RSQrq, DCt, (b, q, d), out, ws, compute_mult, stream)
 
 
 def kkt_tangent_call(torch, plan, layout, N, nprob, p0, count, ndir, BAbt, RSQrq, DCt, db, dq, dd, out, ws,
@@ -143,19 +152,8 @@ def kkt_tangent_call(torch, plan, layout, N, nprob, p0, count, ndir, BAbt, RSQrq
     """hpmpc_mi355x_kkt_tangent_batch on torch tensors, after checking the shapes of the per-set arrays: db, dq
     (nprob, ndir, N+1, 16), dd (nprob, ndir, N+1, 32), each or all None (a zero direction); ``out`` from
     kkt_buffers(ndir), whose ux / pi / lam / t receive dux / dpi / dlam / dt.  Returns the library's code."""
-    for name, x, w in (("db", db, 16), ("dq", dq, 16), ("dd", dd, 32)):
-        if x is None:
-            continue
-        if tuple(x.shape) != (nprob, ndir, N + 1, w) or x.dtype != torch.float64 or not x.is_contiguous():
-            raise ValueError(f"{name}: contiguous float64 tensor of shape {(nprob, ndir, N + 1, w)} expected")
-    for name, w in (("ux", 16), ("pi", 16), ("lam", 32), ("t", 32)):
-        if tuple(out[name].shape) != (nprob, ndir, N + 1, w):
-            raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={ndir}) expected")
-    ptr = lambda x: None if x is None else x.data_ptr()
-    return lib().hpmpc_mi355x_kkt_tangent_batch(
-        plan, layout, nprob, p0, count, ndir, ptr(BAbt), ptr(RSQrq), ptr(DCt), ptr(db), ptr(dq), ptr(dd),
-        ptr(out["ux"]), ptr(out["pi"]), ptr(out["lam"]), ptr(out["t"]), ptr(ws), ptr(out["scratch"]), compute_mult,
-        stream)
+    return _set_call(lib().hpmpc_mi355x_kkt_tangent_batch, ("db", "dq", "dd"), ("db", "dq", "dd"), torch, plan, layout,
+                     N, nprob, p0, count, ndir, BAbt, RSQrq, DCt, (db, dq, dd), out, ws, compute_mult, stream)
 
 
 class BatchSolver:

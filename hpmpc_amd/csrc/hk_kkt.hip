@@ -9,6 +9,7 @@
 // (hk_kkt_body.h), so a set's result does not depend on nrhs or on what else is in the launch.
 #include "hk_kkt_args.h"
 #include "hk_kkt_body.h"
+#include "hk_kkt_launch.h"
 #include "hk_launch.h"
 
 template <class FX>
@@ -21,7 +22,9 @@ __global__ __launch_bounds__(64) void hk_kkt_rhs(KArgs a, KktArgs x) {
     const long s = (long)p * x.nrhs + j % x.nrhs;
     const int N = a.N;
     Ws w = carve(a.ws + (long)p * a.sW, N);  // read only: F, t_inv and the backups
-    {  // the ten work vectors: this set's scratch block (KKT_SCRATCH_V16 / _V32, hk_kkt_args.h)
+    // The ten work vectors: this set's scratch block.  This is carve_set (hk_kkt_args.h) written out: the kernel's
+    // register allocation follows the form of these lines, and with them its code is the measured one.
+    {
         const long n16 = (long)(N + 1) * V16, n32 = (long)(N + 1) * V32;
         double* S = x.scratch + s * x.sS;
         w.res_q = S;
@@ -46,20 +49,7 @@ __global__ __launch_bounds__(64) void hk_kkt_rhs(KArgs a, KktArgs x) {
     kkt_body<FX, true>(a, io, &sm, bt, w, v);
 }
 
-template <class FX>
-static int kkt_rhs_launch_t(const KArgs* a, const KktArgs* x, int count, hipStream_t stream) {
-    // the launch guard (hk_launch_guard.h): LDS tables, private segment against the stack limit, launch bound
-    static const HkKernelLimits lim(reinterpret_cast<const void*>(&hk_kkt_rhs<FX>));
-    const size_t lds = lds_table_bytes(a->N);
-    if (const int e = lim.check(lds, 64)) return e;
-    hipLaunchKernelGGL(hk_kkt_rhs<FX>, dim3((unsigned)count * (unsigned)x->nrhs), dim3(64), lds, stream, *a, *x);
-    return (int)hipGetLastError();
-}
-
-// The compiled inner-stage class is the tile plan's (KArgs.fixcls), as in hk_launch.
 extern "C" int hk_kkt_rhs_launch(const KArgs* a, const KktArgs* x, int count, hipStream_t stream) {
-    if (count <= 0 || x->nrhs <= 0) return 0;
-    return with_fixcls(a->fixcls, [&](auto fx) {
-        return kkt_rhs_launch_t<typename decltype(fx)::type>(a, x, count, stream);
-    });
+    return kkt_sets_launch(a, x, count, x->nrhs, stream,
+                           [](auto fx) { return &hk_kkt_rhs<typename decltype(fx)::type>; });
 }

@@ -6,6 +6,8 @@
 // sV32 between SETS, vb / vq (nullable) the sets' b and q with sV16 between sets.  Set s = p * nrhs + r belongs to
 // problem p.  This block adds what KArgs has no field for.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include "hpmpc_kargs.h"
 
 // Scratch of one set, in carve order: res_q, res_b, qx, dux, dpi, Pb (V16 per stage), then res_d, res_m, dt, dlam (V32
@@ -22,3 +24,13 @@ struct KktArgs {
     double* scratch;  // nprob * nrhs blocks of sS doubles
     long long sS;
 };
+
+// The ten work vectors of the set whose scratch block starts at S (hk_kkt_tan; hk_kkt_rhs writes the same lines out).
+struct KktSet {
+    double *res_q, *res_b, *qx, *dux, *dpi, *Pb, *res_d, *res_m, *dt, *dlam;
+};
+__host__ __device__ inline KktSet carve_set(double* S, int N) {
+    const long long n16 = (long long)(N + 1) * V16, n32 = (long long)(N + 1) * V32;
+    double* S32 = S + KKT_SCRATCH_V16 * n16;
+    return {S, S + n16, S + 2 * n16, S + 3 * n16, S + 4 * n16, S + 5 * n16, S32, S32 + n32, S32 + 2 * n32, S32 + 3 * n32};
+}

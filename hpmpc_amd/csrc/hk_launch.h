@@ -11,8 +11,9 @@ struct KktArgs;
 struct SoftArgs;
 struct SoftResArgs;
 struct WideIpmArgs;
+struct TanArgs;
 struct OcpPackArgs;
-struct OcpFinishArgs;
+struct OcpUnpackArgs;
 
 extern "C" {
 // hpmpc_kernels.hip: the tile kernels (which: HkLaunch) and the compiled inner-stage class of a stage size
@@ -28,10 +29,13 @@ int hk_soft_res_launch(const SoftResArgs* a, hipStream_t stream);
 int hk_soft_ipm_launch(const KArgs* a, const SoftArgs* s, int count, hipStream_t stream);
 // hk_kkt.hip: the batched KKT re-solve, x->nrhs right-hand-side sets for each of `count` problems in one launch
 int hk_kkt_rhs_launch(const KArgs* a, const KktArgs* x, int count, hipStream_t stream);
+// hk_tan.hip: the batched KKT tangent solve, x->k.nrhs direction sets for each of `count` problems in one launch
+int hk_kkt_tan_launch(const KArgs* a, const TanArgs* x, int count, hipStream_t stream);
 // hk_wide.hip (which: HkWideLaunch; args: the WideArgs / PcArgs / PxArgs of that kernel) and hk_wide_ipm.hip
 int hk_wide_launch(int which, const void* args, int count, int lds_doubles, hipStream_t stream);
 int hk_wide_ipm_launch(const WideIpmArgs* a, int count, int lds_doubles, hipStream_t stream);
-// hk_ocp.hip: the batched OCP front end, dense data -> lib4 (grid: stages x a->count problems) and iterate -> outputs
+// hk_ocp.hip: the batched OCP front end, dense data -> lib4 (grid: stages x a->count problems) and the iterates of
+// a->count * a->nsets sets -> outputs (with a->res: the finish, one set per problem and the residual norms)
 int hk_ocp_pack_launch(const OcpPackArgs* a, hipStream_t stream);
-int hk_ocp_finish_launch(const OcpFinishArgs* a, hipStream_t stream);
+int hk_ocp_unpack_launch(const OcpUnpackArgs* a, hipStream_t stream);
 }

@@ -1,8 +1,9 @@
 // hk_ocp.hip -- the batched OCP front end's kernels for gfx950: dense problem data (the c_interface.h wrappers' A,
 // B, b, Q, S, R, q, r, lb, ub, C, D, lg, ug) -> lib4 stage blocks and padded bound vectors in the tile plan's
 // packed layout (hk_ocp_pack; hk_ocp_pack_vectors for matrices = 0), and the solver's padded iterate -> the
-// wrappers' outputs with the residual infinity norms (hk_ocp_finish).  All are pure data movement (hk_ocp_finish
-// adds fabs / fmax only).
+// wrappers' outputs (hk_ocp_unpack: with the residual infinity norms for the finish, without them for the sets of a
+// multi-set re-solve).  All are pure data movement (the finish adds fabs / fmax only); the vector placements are
+// those of hk_ocp_place.h.
 //
 // hk_ocp_pack: one 256-thread workgroup per (section, stage, problem); the sections are the stage's BAbt_k block,
 // its RSQrq_k block, and its DCt_k block with d_k (and ux_k).  A section reads only its own dense arrays (at most
@@ -13,15 +14,14 @@
 // rows / columns and the unused part of the 32-double d slot are stored as zeros: every output element is written
 // and the caller's buffers need no initialisation.
 //
-// hk_ocp_finish: one wavefront per problem walks the stages; lane l owns variable l of ux, row l of pi and
-// compact constraint l of lam / t, and keeps the running maxima of |r_q|, |r_b|, |r_d| over exactly the elements
-// outputs() of hpmpc_capi_iface.cpp visits; one butterfly reduction at the end.
+// hk_ocp_unpack: one wavefront per set (the finish: per problem) walks the stages; lane l owns variable l of ux, row
+// l of pi and compact constraint l of lam / t, and for the finish keeps the running maxima of |r_q|, |r_b|, |r_d|
+// over exactly the elements outputs() of hpmpc_capi_iface.cpp visits; one butterfly reduction at the end.
 #include <hip/hip_runtime.h>
 
 #include "hk_launch.h"
 #include "hk_launch_guard.h"
-#include "hk_ocp_args.h"
-#include "hpmpc_kargs.h"
+#include "hk_ocp_place.h"
 
 namespace {
 
@@ -66,18 +66,6 @@ __device__ __forceinline__ double dct_elem(const OcpStage& s, const double* C, c
     return i < s.nu ? dense(D, rm, s.ng, s.nu, j, i) : dense(C, rm, s.ng, s.nx, j, i - s.nu);
 }
 
-// d_k = [lb pnb | ub pnb | lg png | ug png | 0 ..], 32 doubles
-__device__ __forceinline__ double d_elem(const OcpStage& s, const double* lb, const double* ub, const double* lg,
-                                         const double* ug, int e) {
-    if (e < s.pnb) return e < s.nb ? lb[e] : 0.0;
-    e -= s.pnb;
-    if (e < s.pnb) return e < s.nb ? ub[e] : 0.0;
-    e -= s.pnb;
-    if (e < s.png) return e < s.ng ? lg[e] : 0.0;
-    e -= s.png;
-    return e < s.ng ? ug[e] : 0.0;
-}
-
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
@@ -108,7 +96,7 @@ __global__ __launch_bounds__(PACK_THREADS) void hk_ocp_pack(OcpPackArgs a) {
         const int ai = first + (i < cnt ? i : 0);
         P[i] = a.in[ai].p + p * a.in[ai].s + sg->dn[ai];
     }
-    const int nux = s.nu + s.nx, n = sg->n[sec], sd = sg->sd[sec];  // n = 0: the stage has no such block
+    const int n = sg->n[sec], sd = sg->sd[sec];  // n = 0: the stage has no such block
     double* out = a.out[sec] + p * a.sout[sec] + sg->o[sec];
     for (int e = tid; e < n; e += PACK_THREADS) {
         int i, j;
@@ -123,121 +111,89 @@ __global__ __launch_bounds__(PACK_THREADS) void hk_ocp_pack(OcpPackArgs a) {
         out[e] = v;
     }
     if (sec != OCP_SEC_DCT) return;
-    if (tid >= 64 && tid < 64 + V32)
-        a.d[p * a.sV32 + k * V32 + (tid - 64)] = d_elem(s, P[0], P[1], P[4], P[5], tid - 64);
-    if (a.ux && tid >= 128 && tid < 128 + V16) {
-        const int e = tid - 128;
-        double v = 0.0;
-        if (e < s.nu)
-            v = a.u0[p * a.su + s.dn[OCP_r] + e];
-        else if (e < nux)
-            v = a.x0[p * a.sx + s.dn[OCP_q] + (e - s.nu)];
-        a.ux[p * a.sV16 + k * V16 + e] = v;
+    if (tid >= 64 && tid < 64 + V32) {
+        const auto in = [&](int i) { return a.in[i].p + p * a.in[i].s; };
+        const OcpVecs v{nullptr, nullptr, nullptr, in(OCP_lb), in(OCP_ub), in(OCP_lg), in(OCP_ug)};
+        a.d[p * a.sV32 + k * V32 + (tid - 64)] = __longlong_as_double(ocp_d_bits(s, v, tid - 64));
     }
+    if (a.ux && tid >= 128 && tid < 128 + V16)
+        a.ux[p * a.sV16 + k * V16 + (tid - 128)] = ocp_warm_elem(s, a.u0 + p * a.su, a.x0 + p * a.sx, tid - 128);
 }
 
 // matrices = 0: the vector parts alone -- the b row of BAbt_k, the r / q row of RSQrq_k, d_k (and ux_k); every other
-// element stays as it was.  One wavefront per (stage, problem), four stages per workgroup: lanes 0..15 the b row,
-// 16..31 the r / q row, 32..63 the 32 doubles of d_k.  (The three-section grid of hk_ocp_pack would launch 300 k
-// workgroups with 16 to 32 busy threads each here.)
+// element stays as it was.  One wavefront per (stage, problem), four stages per workgroup; lane l stores element l
+// of the stage's seed row (hk_ocp_place.h): lanes 0..15 the b row, 16..31 the r / q row, 32..63 the 32 doubles of
+// d_k.  (The three-section grid of hk_ocp_pack would launch 300 k workgroups with 16 to 32 busy threads each here.)
 __global__ __launch_bounds__(PACK_THREADS) void hk_ocp_pack_vectors(OcpPackArgs a) {
     const unsigned groups = (a.N + 4) / 4;
     const unsigned pi = blockIdx.x / groups;
-    const int k = (blockIdx.x % groups) * 4 + (threadIdx.x >> 6);
+    // the wavefront's stage, as a scalar: the seed row's loads take wave-uniform bases
+    const int k = (blockIdx.x % groups) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (pi >= (unsigned)a.count || k > a.N) return;
     const long p = (long)a.p0 + pi;
     if (p >= a.nprob) return;
     const OcpStage& s = a.st[k];
-    const int l = threadIdx.x & 63, nu = s.nu, nux = s.nu + s.nx;
-    const auto in = [&](int i) { return a.in[i].p + p * a.in[i].s + s.dn[i]; };
+    const int l = threadIdx.x & 63, nux = s.nu + s.nx;
+    const auto in = [&](int i) { return a.in[i].p + p * a.in[i].s; };
+    const OcpVecs v{in(OCP_b), in(OCP_q), in(OCP_r), in(OCP_lb), in(OCP_ub), in(OCP_lg), in(OCP_ug)};
+    const double val = __longlong_as_double(ocp_seed_bits(s, v, l));
     if (l < 16) {
         if (s.n[OCP_SEC_BABT] > 0 && l < s.nx1)
-            a.out[OCP_SEC_BABT][p * a.sout[OCP_SEC_BABT] + s.o[OCP_SEC_BABT] + lib4_at(s.sd[OCP_SEC_BABT], nux, l)] =
-                in(OCP_b)[l];
+            a.out[OCP_SEC_BABT][p * a.sout[OCP_SEC_BABT] + s.o[OCP_SEC_BABT] + lib4_at(s.sd[OCP_SEC_BABT], nux, l)] = val;
     } else if (l < 32) {
-        const int j = l - 16;
-        if (j < nux)
-            a.out[OCP_SEC_RSQ][p * a.sout[OCP_SEC_RSQ] + s.o[OCP_SEC_RSQ] + lib4_at(s.sd[OCP_SEC_RSQ], nux, j)] =
-                j < nu ? in(OCP_r)[j] : in(OCP_q)[j - nu];
+        if (l - 16 < nux)
+            a.out[OCP_SEC_RSQ][p * a.sout[OCP_SEC_RSQ] + s.o[OCP_SEC_RSQ] + lib4_at(s.sd[OCP_SEC_RSQ], nux, l - 16)] = val;
     } else {
-        a.d[p * a.sV32 + k * V32 + (l - 32)] = d_elem(s, in(OCP_lb), in(OCP_ub), in(OCP_lg), in(OCP_ug), l - 32);
+        a.d[p * a.sV32 + k * V32 + (l - 32)] = val;
     }
-    if (a.ux && l < V16) {
-        double v = 0.0;
-        if (l < nu)
-            v = a.u0[p * a.su + s.dn[OCP_r] + l];
-        else if (l < nux)
-            v = a.x0[p * a.sx + s.dn[OCP_q] + (l - nu)];
-        a.ux[p * a.sV16 + k * V16 + l] = v;
-    }
+    if (a.ux && l < V16) a.ux[p * a.sV16 + k * V16 + l] = ocp_warm_elem(s, a.u0 + p * a.su, a.x0 + p * a.sx, l);
 }
 
-__global__ __launch_bounds__(64) void hk_ocp_finish(OcpFinishArgs a) {
-    if (blockIdx.x >= (unsigned)a.count) return;
-    const long p = (long)a.p0 + blockIdx.x;
-    if (p >= a.nprob) return;
+// RES: the finish -- one set per problem (the host's guarantee), and the residual maxima and mu go to a.inf.
+template <bool RES>
+__global__ __launch_bounds__(64) void hk_ocp_unpack(OcpUnpackArgs a) {
+    const unsigned nsets = RES ? 1u : (unsigned)a.nsets;
+    const unsigned pi_ = blockIdx.x / nsets;
+    const long p = (long)a.p0 + pi_;
+    if (pi_ >= (unsigned)a.count || p >= a.nprob) return;
+    const long s = p * nsets + blockIdx.x % nsets;
     const int l = threadIdx.x;
-    const double* d = a.d + p * a.sV32;
-    const double* ux = a.ux + p * a.sV16;
-    const double* pi = a.pi + p * a.sV16;
-    const double* lam = a.lam + p * a.sV32;
-    const double* t = a.t + p * a.sV32;
-    const long n1 = a.N + 1;
-    const double* rq = a.res + p * a.sRes;
-    const double* rb = rq + n1 * V16;
-    const double* rd = rb + n1 * V16;
-    double* u = a.u + p * a.su;
-    double* x = a.x + p * a.sx;
-    double* po = a.po + p * a.sp;
-    double* lamo = a.lamo + p * a.sl;
-    double* to = a.to ? a.to + p * a.sl : nullptr;
+    const double* d = a.d + s * a.sV32;
+    const double* ux = a.ux + s * a.sV16;
+    const double* pi = a.pi + s * a.sV16;
+    const double* lam = a.lam + s * a.sV32;
+    const double* t = a.t + s * a.sV32;
+    const double *rq = nullptr, *rb = nullptr, *rd = nullptr;
+    if constexpr (RES) {
+        rq = a.res + p * a.sRes;
+        rb = rq + (a.N + 1) * V16;
+        rd = rb + (a.N + 1) * V16;
+    }
+    const OcpOut o = ocp_out_at(a.out, s);
     double mq = 0.0, mb = 0.0, md = 0.0;
     for (int k = 0; k <= a.N; k++) {
-        const OcpStage s = a.st[k];
-        const int nux = s.nu + s.nx;
-        if (l < nux) {
-            double v = ux[k * V16 + l];
-            if (l < s.nu) {
-                // the equality-box fix over the leading input boxes: u[idxb[j]] = lb[j] where lb[j] == ub[j]
-                for (int j = 0; j < s.nbu; j++) {
-                    const double lo = d[k * V32 + j], up = d[k * V32 + s.pnb + j];
-                    if (a.idxb[k * 16 + j] == l && lo == up) v = lo;
-                }
-                u[s.dn[OCP_r] + l] = v;
-            } else {
-                x[s.dn[OCP_q] + (l - s.nu)] = v;
-            }
-            mq = fmax(mq, fabs(rq[k * V16 + l]));
-        }
-        if (l < s.nx1) {
-            po[s.dn[OCP_b] + l] = pi[k * V16 + l];
-            mb = fmax(mb, fabs(rb[k * V16 + l]));
-        }
-        if (l < 2 * s.nb + 2 * s.ng) {  // compact [lb nb | ub nb | lg ng | ug ng] from the padded slot
-            int src;
-            if (l < s.nb)
-                src = l;
-            else if (l < 2 * s.nb)
-                src = s.pnb + (l - s.nb);
-            else if (l < 2 * s.nb + s.ng)
-                src = 2 * s.pnb + (l - 2 * s.nb);
-            else
-                src = 2 * s.pnb + s.png + (l - 2 * s.nb - s.ng);
-            const int o = 2 * s.dn[OCP_lb] + 2 * s.dn[OCP_lg] + l;
-            lamo[o] = lam[k * V32 + src];
-            if (to) to[o] = t[k * V32 + src];
-            md = fmax(md, fabs(rd[k * V32 + src]));
+        const OcpStage os = a.st[k];
+        const bool hv = l < os.nu + os.nx, hp = l < os.nx1, hc = l < 2 * os.nb + 2 * os.ng;
+        const int src = k * V32 + compact_src(os, hc ? l : 0);
+        ocp_unpack_store(os, o, l, hv ? ux[k * V16 + l] : 0.0, hp ? pi[k * V16 + l] : 0.0, hc ? lam[src] : 0.0,
+                         hc && o.t ? t[src] : 0.0, d + k * V32, a.idxb + k * 16);
+        if constexpr (RES) {
+            if (hv) mq = fmax(mq, fabs(rq[k * V16 + l]));
+            if (hp) mb = fmax(mb, fabs(rb[k * V16 + l]));
+            if (hc) md = fmax(md, fabs(rd[src]));
         }
     }
-    mq = wave_max(mq);
-    mb = wave_max(mb);
-    md = wave_max(md);
-    if (l == 0) {
-        double* inf = a.inf + 4 * p;
-        inf[0] = mq;
-        inf[1] = mb;
-        inf[2] = md;
-        inf[3] = a.mu[p];
+    if constexpr (RES) {
+        mq = wave_max(mq);
+        mb = wave_max(mb);
+        md = wave_max(md);
+        if (l == 0) {
+            double* inf = a.inf + 4 * p;
+            inf[0] = mq;
+            inf[1] = mb;
+            inf[2] = md;
+            inf[3] = a.mu[p];
+        }
     }
 }
 
@@ -255,10 +211,16 @@ extern "C" int hk_ocp_pack_launch(const OcpPackArgs* a, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-extern "C" int hk_ocp_finish_launch(const OcpFinishArgs* a, hipStream_t stream) {
-    if (a->count <= 0) return 0;
-    static const HkKernelLimits lim(reinterpret_cast<const void*>(&hk_ocp_finish));
-    if (const int e = lim.check(0, 64)) return e;
-    hipLaunchKernelGGL(hk_ocp_finish, dim3(a->count), dim3(64), 0, stream, *a);
+// a->res set: the finish (residual maxima; one set per problem), else the plain unpack of count * nsets sets
+extern "C" int hk_ocp_unpack_launch(const OcpUnpackArgs* a, hipStream_t stream) {
+    if (a->count <= 0 || a->nsets <= 0) return 0;
+    if (a->res && a->nsets != 1) return HK_LAUNCH_REFUSED;
+    const auto kernel = a->res ? &hk_ocp_unpack<true> : &hk_ocp_unpack<false>;
+    static const HkKernelLimits lim[2] = {HkKernelLimits(reinterpret_cast<const void*>(&hk_ocp_unpack<false>)),
+                                          HkKernelLimits(reinterpret_cast<const void*>(&hk_ocp_unpack<true>))};
+    if (const int e = lim[a->res ? 1 : 0].check(0, 64)) return e;
+    const long long blocks = (long long)a->count * a->nsets;
+    if (blocks > 0x7fffffffLL) return HK_LAUNCH_REFUSED;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, stream, *a);
     return (int)hipGetLastError();
 }

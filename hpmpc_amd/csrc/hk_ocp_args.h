@@ -46,15 +46,25 @@ struct OcpPackArgs {
     long long sV16;
 };
 
-struct OcpFinishArgs {
-    int N, nprob, p0, count;
+// The dense outputs: u, x, pi shaped like r, q, b, lam / t compact [lb nb | ub nb | lg ng | ug ng] per stage, with the
+// doubles between problems (or sets).  t is nullable.  Filled from the plan by ocp_out (hk_ocp_plan.h).
+struct OcpOut {
+    double *u, *x, *pi, *lam, *t;
+    long long su, sx, sp, sl;
+};
+
+// hk_ocp_unpack: the padded iterate of nprob * nsets sets -> the dense outputs (set s = p * nsets + r; sV16 / sV32
+// and the output strides are between sets).  With `res` (hpmpc_mi355x_ocp_finish_batch; nsets = 1) also the
+// residual infinity norms.
+struct OcpUnpackArgs {
+    int N, nprob, p0, count, nsets;
     const OcpStage* st;
     const int* idxb;  // (N+1) * 16
     const double *d, *ux, *pi, *lam, *t;
     long long sV16, sV32;
-    const double* res;  // hk_res output per problem: [rq | rb] V16 per stage, [rd | rm] V32 per stage
+    OcpOut out;
+    const double* res;  // hk_res output per problem: [rq | rb] V16 per stage, [rd | rm] V32 per stage; null: no norms
     long long sRes;
     const double* mu;  // per problem
-    double *u, *x, *po, *lamo, *to, *inf;  // to: nullable
-    long long su, sx, sp, sl;
+    double* inf;       // 4 per problem
 };

@@ -1,5 +1,5 @@
 // hk_ocp_plan.h -- the OCP plan of the batched OCP front end, shared by hpmpc_capi_ocp.cpp (which creates it) and
-// hpmpc_capi_tan.cpp (the tangent call and the multi-set finish): a tile plan, whose packed default layout the lib4
+// hpmpc_capi_kkt.cpp (the dense tangent call): a tile plan, whose packed default layout the lib4
 // and vector arrays follow, and the device tables of stage sizes, dense offsets (OcpStage, hk_ocp_args.h) and box
 // indices.
 #pragma once
@@ -18,3 +18,11 @@ struct hpmpc_mi355x_ocp_plan {
     DevTable<OcpStage> d_st;
     DevTable<int> d_idx;
 };
+
+// The dense outputs of a call on plan O, and whether every one the plan has an element of is given (t: when asked).
+inline OcpOut ocp_out(const hpmpc_mi355x_ocp_plan* O, double* u, double* x, double* pi, double* lam, double* t) {
+    return {u, x, pi, lam, t, O->su, O->sx, O->sp, O->sl};
+}
+inline bool ocp_out_ok(const OcpOut& o, bool need_t) {
+    return (o.su == 0 || o.u) && (o.sx == 0 || o.x) && (o.sp == 0 || o.pi) && (o.sl == 0 || (o.lam && (o.t || !need_t)));
+}

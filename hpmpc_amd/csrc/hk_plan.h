@@ -3,9 +3,10 @@
 // functions and call checks below), hpmpc_capi_queue.cpp (the problem queue), hpmpc_capi_dropin.cpp (reference-named
 // hard-constraint entry points; defines the arena functions), hpmpc_capi_soft.cpp (soft-constraint IPM and residual;
 // defines the soft refusals, layout and IPM setup), hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM),
-// hpmpc_capi_ocp.cpp (the batched OCP front end), hpmpc_capi_kkt.cpp (the batched KKT re-solve) and
-// hpmpc_capi_tan.cpp (its tangent solve and the multi-set finish; through hk_ocp_plan.h).
+// hpmpc_capi_ocp.cpp (the batched OCP front end) and hpmpc_capi_kkt.cpp (the batched KKT re-solve and its tangent
+// solve; through hk_ocp_plan.h).
 #pragma once
+#include <climits>
 #include <mutex>
 #include <vector>
 
@@ -85,6 +86,13 @@ void idxb_table(int N, const int* nb, const int* const* idxb, int* out);
 bool range_ok(const void* plan, int nprob, int p0, int count, const char* who);
 int null_array(const char* who);
 int launch_error(int e, const char* what);
+// n sets per problem (right-hand sides, directions): the grid is count * n workgroups and a set index is an int.
+// False: g_err set, with the message `what`.
+inline bool sets_ok(int nprob, int n, const char* what) {
+    if (n >= 1 && (long long)nprob * n <= INT_MAX) return true;
+    hk_set_error(HPMPC_MI355X_EUNSUPPORTED, what);
+    return false;
+}
 // The argument block of a batched call: the plan's tables and strides, the layout (null: the packed default; a
 // layout's first use uploads its stage table) and DCt.  A call that carries no DCt array refuses a plan with
 // ng > 0 (DCT_NONE); one that does passes it on when the plan has general constraints (DCT_ARRAY).  False: g_err set.

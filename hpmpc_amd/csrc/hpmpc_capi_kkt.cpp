@@ -1,40 +1,47 @@
-// hpmpc_capi_kkt.cpp -- the batched KKT re-solve: hpmpc_mi355x_kkt_new_rhs_batch and hpmpc_mi355x_ocp_kkt_batch,
-// d_kkt_solve_new_rhs_res_mpc_hard_tv (mpc_solvers/d_ip2_res_hard.c:1922-2299) on device-resident batches, nrhs
-// right-hand-side sets per problem in one launch of hk_kkt_rhs (hk_kkt.hip).  The workspaces an IPM left
+// hpmpc_capi_kkt.cpp -- the batched calls on the factor an IPM left, many sets per problem in one launch: the KKT
+// re-solve hpmpc_mi355x_kkt_new_rhs_batch and hpmpc_mi355x_ocp_kkt_batch, d_kkt_solve_new_rhs_res_mpc_hard_tv
+// (mpc_solvers/d_ip2_res_hard.c:1922-2299) on device-resident batches, nrhs right-hand-side sets per problem
+// (hk_kkt_rhs, hk_kkt.hip); and its linear part, the KKT tangent solve hpmpc_mi355x_kkt_tangent_batch (padded
+// directions and results, the re-solve's layouts) and hpmpc_mi355x_ocp_tangent_batch (dense directions and results on
+// an OCP plan), ndir direction sets per problem (hk_kkt_tan, hk_tan.hip).  The workspaces an IPM left
 // (hpmpc_mi355x_ipm_batch, _ipm_solo, _ocp_ipm_batch) are read only; each set's work vectors live in the caller's
-// scratch (kkt_scratch_doubles, hk_kkt_args.h).  The core call carries a DCt array, so it takes tile plans with
+// scratch (kkt_scratch_doubles, hk_kkt_args.h).  The core calls carry a DCt array, so they take tile plans with
 // general constraints (batch_args with DCT_ARRAY).
-#include <climits>
-
-#include "hk_kkt_args.h"
-#include "hk_plan.h"
+#include "hk_ocp_plan.h"
+#include "hk_tan_args.h"
 
 extern "C" long long hpmpc_mi355x_kkt_scratch_doubles(const hpmpc_mi355x_plan* P) {
     return P ? kkt_scratch_doubles(P->N) : 0;
 }
 
-extern "C" int hpmpc_mi355x_kkt_new_rhs_batch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob,
-                                              int p0, int count, int nrhs, const double* BAbt, const double* RSQrq,
-                                              const double* DCt, const double* b, const double* q, const double* d,
-                                              double* ux, double* pi, double* lam, double* t, const double* ws,
-                                              double* scratch, int compute_mult, void* stream) {
+namespace {
+
+// The checks and the argument blocks these calls share.  arrays: the caller's own required arrays are all there.
+// False: nothing to launch, g_err holds the call's return (an error, or 0 for a range without a problem).
+bool sets_args(KArgs& a, KktArgs& x, const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob, int p0,
+               int count, int nsets, const double* BAbt, const double* RSQrq, const double* DCt, const double* ws,
+               double* scratch, bool arrays, int compute_mult, const char* who, const char* sets_msg) {
     g_err = 0;
-    const char* who = "hpmpc_mi355x_kkt_new_rhs_batch";
-    if (!range_ok(plan, nprob, p0, count, who)) return g_err;
-    // the grid is count * nrhs workgroups and a set index is an int
-    if (nrhs < 1 || (long long)nprob * nrhs > INT_MAX) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_kkt_new_rhs_batch: nrhs");
-        return g_err;
+    if (!range_ok(plan, nprob, p0, count, who) || !sets_ok(nprob, nsets, sets_msg) || count == 0) return false;
+    if (!BAbt || !RSQrq || !ws || !scratch || !arrays || (plan->ngt && !DCt)) {
+        null_array(who);
+        return false;
     }
-    if (count == 0) return 0;
-    if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !ws || !scratch || (plan->ngt && !DCt))
-        return null_array(who);
-    KArgs a;
-    if (!batch_args(a, plan, lay, nprob, p0, DCT_ARRAY, DCt)) return g_err;
+    if (!batch_args(a, plan, lay, nprob, p0, DCT_ARRAY, DCt)) return false;
     a.BAbt = BAbt;
     a.RSQ = RSQrq;
-    a.ws = const_cast<double*>(ws);  // hk_kkt_rhs only reads it
-    // the per-set arrays: batch_args' sV16 / sV32 are the strides between sets
+    a.ws = const_cast<double*>(ws);  // the kernels only read it
+    a.compute_mult = compute_mult;
+    memset(&x, 0, sizeof x);
+    x.nrhs = nsets;
+    x.scratch = scratch;
+    x.sS = kkt_scratch_doubles(plan->N);
+    return true;
+}
+
+// the per-set arrays: batch_args' sV16 / sV32 are the strides between sets
+void set_arrays(KArgs& a, const double* b, const double* q, const double* d, double* ux, double* pi, double* lam,
+                double* t) {
     a.vb = b;
     a.vq = q;
     a.d = d;
@@ -42,12 +49,21 @@ extern "C" int hpmpc_mi355x_kkt_new_rhs_batch(const hpmpc_mi355x_plan* plan, con
     a.pi = pi;
     a.lam = lam;
     a.t = t;
-    a.compute_mult = compute_mult;
+}
+
+}  // namespace
+
+extern "C" int hpmpc_mi355x_kkt_new_rhs_batch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob,
+                                              int p0, int count, int nrhs, const double* BAbt, const double* RSQrq,
+                                              const double* DCt, const double* b, const double* q, const double* d,
+                                              double* ux, double* pi, double* lam, double* t, const double* ws,
+                                              double* scratch, int compute_mult, void* stream) {
+    KArgs a;
     KktArgs x;
-    memset(&x, 0, sizeof x);
-    x.nrhs = nrhs;
-    x.scratch = scratch;
-    x.sS = kkt_scratch_doubles(plan->N);
+    if (!sets_args(a, x, plan, lay, nprob, p0, count, nrhs, BAbt, RSQrq, DCt, ws, scratch, d && ux && pi && lam && t,
+                   compute_mult, "hpmpc_mi355x_kkt_new_rhs_batch", "hpmpc_mi355x_kkt_new_rhs_batch: nrhs"))
+        return g_err;
+    set_arrays(a, b, q, d, ux, pi, lam, t);
     if (const int e = hk_kkt_rhs_launch(&a, &x, count, (hipStream_t)stream))
         return launch_error(e, "hk_kkt_rhs launch failed");
     return g_err = 0;
@@ -59,11 +75,69 @@ extern "C" int hpmpc_mi355x_ocp_kkt_batch(const hpmpc_mi355x_ocp_plan* O, int np
                                           const double* BAbt, const double* RSQrq, const double* DCt, const double* d,
                                           double* ux, double* pi, double* lam, double* t, const double* ws,
                                           double* scratch, void* stream) {
-    const hpmpc_mi355x_plan* P = hpmpc_mi355x_ocp_tile_plan(O);
-    if (!P) {
+    if (!O) {
         hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_kkt_batch: plan");
         return g_err;
     }
-    return hpmpc_mi355x_kkt_new_rhs_batch(P, nullptr, nprob, p0, count, 1, BAbt, RSQrq, DCt, nullptr, nullptr, d, ux,
-                                          pi, lam, t, ws, scratch, 1, stream);
+    return hpmpc_mi355x_kkt_new_rhs_batch(O->tile.get(), nullptr, nprob, p0, count, 1, BAbt, RSQrq, DCt, nullptr,
+                                          nullptr, d, ux, pi, lam, t, ws, scratch, 1, stream);
+}
+
+// A null direction is zero.
+extern "C" int hpmpc_mi355x_kkt_tangent_batch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob,
+                                              int p0, int count, int ndir, const double* BAbt, const double* RSQrq,
+                                              const double* DCt, const double* db, const double* dq, const double* dd,
+                                              double* dux, double* dpi, double* dlam, double* dt, const double* ws,
+                                              double* scratch, int compute_mult, void* stream) {
+    KArgs a;
+    TanArgs x;
+    memset(&x, 0, sizeof x);
+    if (!sets_args(a, x.k, plan, lay, nprob, p0, count, ndir, BAbt, RSQrq, DCt, ws, scratch, dux && dpi && dlam && dt,
+                   compute_mult, "hpmpc_mi355x_kkt_tangent_batch", "hpmpc_mi355x tangent call: ndir"))
+        return g_err;
+    set_arrays(a, db, dq, dd, dux, dpi, dlam, dt);
+    if (const int e = hk_kkt_tan_launch(&a, &x, count, (hipStream_t)stream))
+        return launch_error(e, "hk_kkt_tan launch failed");
+    return g_err = 0;
+}
+
+extern "C" int hpmpc_mi355x_ocp_tangent_batch(const hpmpc_mi355x_ocp_plan* O, const hpmpc_mi355x_ocp_data* dirs,
+                                              int nprob, int p0, int count, int ndir, const double* BAbt,
+                                              const double* RSQrq, const double* DCt, double* du, double* dx,
+                                              double* dpi, double* dlam, double* dt, const double* ws, double* scratch,
+                                              int compute_mult, void* stream) {
+    if (!O) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_tangent_batch: plan");
+        return g_err;
+    }
+    KArgs a;
+    TanArgs x;
+    memset(&x, 0, sizeof x);
+    const OcpOut out = ocp_out(O, du, dx, dpi, dlam, dt);
+    if (!sets_args(a, x.k, O->tile.get(), nullptr, nprob, p0, count, ndir, BAbt, RSQrq, DCt, ws, scratch,
+                   dirs && ocp_out_ok(out, true), compute_mult, "hpmpc_mi355x_ocp_tangent_batch",
+                   "hpmpc_mi355x tangent call: ndir"))
+        return g_err;
+    for (int i = 0; i < OCP_NARR; i++) {
+        const bool vec = i == OCP_b || i == OCP_q || i == OCP_r || i == OCP_lb || i == OCP_ub || i == OCP_lg ||
+                         i == OCP_ug;
+        if (!vec && dirs->ptr[i]) {
+            hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_tangent_batch: matrix directions (A, B, Q, S, R, "
+                                                    "C, D) are not supported");
+            return g_err;
+        }
+        if (vec && dirs->ptr[i] && dirs->stride[i] < 0) {
+            hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_tangent_batch: negative stride");
+            return g_err;
+        }
+        if (vec && O->dense[i] > 0) {  // a vector the plan has no element of is never read
+            x.in[i].p = dirs->ptr[i];
+            x.in[i].s = dirs->stride[i];
+        }
+    }
+    x.ost = O->d_st.get();
+    x.out = out;
+    if (const int e = hk_kkt_tan_launch(&a, &x, count, (hipStream_t)stream))
+        return launch_error(e, "hk_kkt_tan launch failed");
+    return g_err = 0;
 }

@@ -3,7 +3,8 @@
 // does what pack_problem() of hpmpc_capi_iface.cpp does per problem on the host (hk_ocp_pack, hk_ocp.hip),
 // hpmpc_mi355x_ocp_ipm_batch is hpmpc_mi355x_ipm_batch's pass sequence with the DCt array set (so general
 // constraints are served here), and hpmpc_mi355x_ocp_finish_batch does what outputs() does: the plain residuals
-// (hk_res with res_plain, into a scratch of its own, so the IPM's factor in ws survives) and hk_ocp_finish.
+// (hk_res with res_plain, into a scratch of its own, so the IPM's factor in ws survives) and hk_ocp_unpack, which
+// hpmpc_mi355x_ocp_unpack_sets runs without the residual norms for the sets of a multi-set re-solve.
 //
 // An OCP plan wraps a tile plan -- the lib4 / vector arrays are in its packed default layout -- and the device
 // table of stage sizes and dense offsets (OcpStage, hk_ocp_args.h).  Dense arrays: per problem the stage blocks
@@ -201,6 +202,37 @@ extern "C" int hpmpc_mi355x_ocp_ipm_batch(const hpmpc_mi355x_ocp_plan* O, int np
                    compute_mult, kk, ret, stat, K_IPM, stream);
 }
 
+// hk_ocp_unpack on `nsets` sets per problem of the padded d, ux, pi, lam, t (sV16 / sV32 between sets); res / mu /
+// inf set: the finish's residual norms (one set per problem).
+static int ocp_unpack(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nsets, const double* d,
+                      const double* ux, const double* pi, const double* lam, const double* t, const OcpOut& out,
+                      const double* res, const double* mu, double* inf, void* stream, const char* failed) {
+    const long long n1 = O->N + 1;
+    OcpUnpackArgs f;
+    memset(&f, 0, sizeof f);
+    f.N = O->N;
+    f.nprob = nprob;
+    f.p0 = p0;
+    f.count = count;
+    f.nsets = nsets;
+    f.st = O->d_st.get();
+    f.idxb = O->d_idx.get();
+    f.d = d;
+    f.ux = ux;
+    f.pi = pi;
+    f.lam = lam;
+    f.t = t;
+    f.sV16 = n1 * V16;
+    f.sV32 = n1 * V32;
+    f.out = out;
+    f.res = res;
+    f.sRes = O->sRes;
+    f.mu = mu;
+    f.inf = inf;
+    if (const int e = hk_ocp_unpack_launch(&f, (hipStream_t)stream)) return launch_error(e, failed);
+    return g_err = 0;
+}
+
 // res: nprob residual images of 2 (N+1) V16 + 2 (N+1) V32 doubles ([rq | rb | rd | rm], hk_res's ws / sW), then the
 // nprob values of mu -- within the nprob * sizes[res] doubles the caller allocates.
 extern "C" int hpmpc_mi355x_ocp_finish_batch(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count,
@@ -212,10 +244,10 @@ extern "C" int hpmpc_mi355x_ocp_finish_batch(const hpmpc_mi355x_ocp_plan* O, int
     const char* who = "hpmpc_mi355x_ocp_finish_batch";
     if (!range_ok(O, nprob, p0, count, who)) return g_err;
     if (count == 0) return 0;
+    const OcpOut out = ocp_out(O, u, x, pi_out, lam_out, t_out);
     if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !res || !inf_norm_res || (O->tile->ngt && !DCt) ||
-        (O->su > 0 && !u) || (O->sx > 0 && !x) || (O->sp > 0 && !pi_out) || (O->sl > 0 && !lam_out))
+        !ocp_out_ok(out, false))
         return null_array(who);
-    const long long n1 = O->N + 1;
     double* mu = res + (long long)nprob * O->sRes;
     KArgs a;
     if (!batch_args(a, O->tile.get(), nullptr, nprob, p0, DCT_ARRAY, DCt)) return g_err;
@@ -231,34 +263,23 @@ extern "C" int hpmpc_mi355x_ocp_finish_batch(const hpmpc_mi355x_ocp_plan* O, int
     a.res_plain = 1;  // d_res_mpc_hard_tv
     a.mu_out = mu;
     if (const int e = hk_launch(K_RES, &a, count, (hipStream_t)stream)) return launch_error(e, "hk_res launch failed");
-    OcpFinishArgs f;
-    memset(&f, 0, sizeof f);
-    f.N = O->N;
-    f.nprob = nprob;
-    f.p0 = p0;
-    f.count = count;
-    f.st = O->d_st.get();
-    f.idxb = O->d_idx.get();
-    f.d = d;
-    f.ux = ux;
-    f.pi = pi;
-    f.lam = lam;
-    f.t = t;
-    f.sV16 = n1 * V16;
-    f.sV32 = n1 * V32;
-    f.res = res;
-    f.sRes = O->sRes;
-    f.mu = mu;
-    f.u = u;
-    f.x = x;
-    f.po = pi_out;
-    f.lamo = lam_out;
-    f.to = t_out;
-    f.inf = inf_norm_res;
-    f.su = O->su;
-    f.sx = O->sx;
-    f.sp = O->sp;
-    f.sl = O->sl;
-    if (const int e = hk_ocp_finish_launch(&f, (hipStream_t)stream)) return launch_error(e, "hk_ocp_finish launch failed");
-    return g_err = 0;
+    return ocp_unpack(O, nprob, p0, count, 1, d, ux, pi, lam, t, out, res, mu, inf_norm_res, stream,
+                      "hk_ocp_finish launch failed");
+}
+
+// The multi-set finish of re-solved sets: the same placement and equality-box fix (from each set's own d), nrhs
+// sets per problem, no residuals.
+extern "C" int hpmpc_mi355x_ocp_unpack_sets(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nrhs,
+                                            const double* d, const double* ux, const double* pi, const double* lam,
+                                            const double* t, double* u, double* x, double* pi_out, double* lam_out,
+                                            double* t_out, void* stream) {
+    g_err = 0;
+    const char* who = "hpmpc_mi355x_ocp_unpack_sets";
+    if (!range_ok(O, nprob, p0, count, who)) return g_err;
+    if (!sets_ok(nprob, nrhs, "hpmpc_mi355x_ocp_unpack_sets: nrhs")) return g_err;
+    if (count == 0) return 0;
+    const OcpOut out = ocp_out(O, u, x, pi_out, lam_out, t_out);
+    if (!d || !ux || !pi || !lam || !t || !ocp_out_ok(out, false)) return null_array(who);
+    return ocp_unpack(O, nprob, p0, count, nrhs, d, ux, pi, lam, t, out, nullptr, nullptr, nullptr, stream,
+                      "hk_ocp_unpack_sets launch failed");
 }

@@ -252,17 +252,31 @@ class OcpBatchSolver:
         raise ValueError(f"{what}: shape ({self.nprob}, {n}) or ({n},) with unit inner stride expected, got "
                          f"{tuple(x.shape)}")
 
-    def data_struct(self, data):
+    def _ocp_data(self, data, one):
+        """hpmpc_mi355x_ocp_data of {key: tensor}: ``one(key, x, n)`` gives (pointer, stride) of a given array of
+        sizes[key] = n, or raises; a missing (or None) one is null."""
         ds = _OcpData()
         for i, key in enumerate(KEYS):
-            n = self.sizes[key]
-            if n == 0 and data.get(key) is None:
-                ds.ptr[i], ds.stride[i] = None, 0
-                continue
-            if data.get(key) is None:
-                raise ValueError(f"dense array {key} missing")
-            ds.ptr[i], ds.stride[i] = self._vec(data[key], n, key)
+            x = data.get(key)
+            ds.ptr[i], ds.stride[i] = (None, 0) if x is None else one(key, x, self.sizes[key])
         return ds
+
+    def data_struct(self, data):
+        for key in KEYS:
+            if self.sizes[key] and data.get(key) is None:
+                raise ValueError(f"dense array {key} missing")
+        return self._ocp_data(data, lambda key, x, n: self._vec(x, n, key))
+
+    def _lib4(self, ptr=True):
+        """The packed BAbt, RSQrq and DCt (None without general constraints), as pointers or as tensors."""
+        arrays = self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None
+        return tuple(None if x is None else x.data_ptr() for x in arrays) if ptr else arrays
+
+    def _sized(self, o):
+        """The tensors u, x, pi, lam, t of ``o``, allocated with at least one element, cut to their sizes."""
+        s = self.sizes
+        return dict(u=o["u"][..., :s["u"]], x=o["x"][..., :s["x"]], pi=o["pi"][..., :s["pi_out"]],
+                    lam=o["lam"][..., :s["lam_out"]], t=o["t"][..., :s["lam_out"]])
 
     def pack(self, data, matrices=True, warm=None, p0=0, count=None):
         """Dense device tensors -> BAbt, RSQrq, DCt, d (hk_ocp_pack).  ``data``: {key: tensor (nprob, size), or
@@ -278,18 +292,15 @@ class OcpBatchSolver:
                 raise ValueError("warm u / x: contiguous (nprob, size) tensors expected")
             ux = self.ux.data_ptr()
         check(lib().hpmpc_mi355x_ocp_pack_batch(
-            self.plan, C.byref(ds), 1 if matrices else 0, self.nprob, p0, count, self.BAbt.data_ptr(),
-            self.RSQrq.data_ptr(), self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), u0, x0, ux,
-            self._stream()), "hpmpc_mi355x_ocp_pack_batch")
+            self.plan, C.byref(ds), 1 if matrices else 0, self.nprob, p0, count, *self._lib4(), self.d.data_ptr(), u0,
+            x0, ux, self._stream()), "hpmpc_mi355x_ocp_pack_batch")
 
     def solve(self, mu0=2.0, mu_tol=1e-10, alpha_min=1e-8, warm_start=0, p0=0, count=None):
         """d_ip2_res_mpc_hard_tv on the packed batch (mu0 > 0: one value for the batch)."""
         p0, count = self._range(p0, count)
         check(lib().hpmpc_mi355x_ocp_ipm_batch(
-            self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
-            self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
-            self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(), self.k_max, mu0, mu_tol,
-            alpha_min, warm_start, 1, self.kk.data_ptr(), self.ret.data_ptr(), self.stat.data_ptr(),
+            self.plan, self.nprob, p0, count, *self._lib4(), self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(),
+            self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(), self.k_max, mu0, mu_tol, alpha_min, warm_start, 1, self.kk.data_ptr(), self.ret.data_ptr(), self.stat.data_ptr(),
             self._stream()), "hpmpc_mi355x_ocp_ipm_batch")
 
     def kkt_buffers(self, nrhs: int = 1) -> dict:
@@ -314,10 +325,8 @@ class OcpBatchSolver:
         p0, count = self._range(p0, count)
         self.pack(data, matrices=False, p0=p0, count=count)
         check(lib().hpmpc_mi355x_ocp_kkt_batch(
-            self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
-            self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
-            self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(),
-            self.kkt_buffers(1)["scratch"].data_ptr(), self._stream()), "hpmpc_mi355x_ocp_kkt_batch")
+            self.plan, self.nprob, p0, count, *self._lib4(), self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(),
+            self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(), self.kkt_buffers(1)["scratch"].data_ptr(), self._stream()), "hpmpc_mi355x_ocp_kkt_batch")
 
     def kkt_sets(self, b, q, d, nrhs=1, p0=0, count=None, compute_mult=1, dense=False):
         """hpmpc_mi355x_kkt_new_rhs_batch with the tile plan on the packed arrays: ``nrhs`` right-hand-side sets per
@@ -334,7 +343,7 @@ class OcpBatchSolver:
         p0, count = self._range(p0, count)
         out = self.kkt_buffers(nrhs)
         check(kkt_sets_call(self.torch, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), None, self.N, self.nprob, p0,
-                            count, nrhs, self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None, b, q, d, out,
+                            count, nrhs, *self._lib4(ptr=False), b, q, d, out,
                             self.ws, compute_mult, self._stream()), "hpmpc_mi355x_kkt_new_rhs_batch")
         if not dense:
             return out["ux"], out["pi"], out["lam"], out["t"]
@@ -358,11 +367,6 @@ class OcpBatchSolver:
                                t=new(s["lam_out"]))
         return bufs[nsets]
 
-    def _sized(self, o):
-        s = self.sizes
-        return dict(u=o["u"][:, :, :s["u"]], x=o["x"][:, :, :s["x"]], pi=o["pi"][:, :, :s["pi_out"]],
-                    lam=o["lam"][:, :, :s["lam_out"]], t=o["t"][:, :, :s["lam_out"]])
-
     def tangent(self, dirs, ndir, p0=0, count=None, compute_mult=1):
         """Forward sensitivities of the re-solved plan (hpmpc_mi355x_ocp_tangent_batch): the directional derivative
         of what resolve() computes with respect to its b, q, r and bounds, ``ndir`` directions per problem in one
@@ -374,22 +378,18 @@ class OcpBatchSolver:
         back as zeros.  Neither ws nor the solver's data or iterate is written."""
         torch = self.torch
         p0, count = self._range(p0, count)
-        ds = _OcpData()
-        for i, key in enumerate(KEYS):
-            x = dirs.get(key)
-            if x is None:
-                ds.ptr[i], ds.stride[i] = None, 0
-                continue
-            n = self.sizes[key]
+
+        def direction(key, x, n):
             if x.dtype != torch.float64 or x.device.type != self.dev.type or not x.is_contiguous() or \
                     (key in VEC_KEYS and tuple(x.shape) != (self.nprob, ndir, n)):
                 raise ValueError(f"direction {key}: contiguous float64 tensor ({self.nprob}, {ndir}, {n}) on "
                                  f"{self.dev} expected")
-            ds.ptr[i], ds.stride[i] = x.data_ptr(), n
+            return x.data_ptr(), n
+
+        ds = self._ocp_data(dirs, direction)
         o = self.set_buffers(ndir)
         check(lib().hpmpc_mi355x_ocp_tangent_batch(
-            self.plan, C.byref(ds), self.nprob, p0, count, ndir, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
-            self.DCt.data_ptr() if self.sizes["DCt"] else None, o["u"].data_ptr(), o["x"].data_ptr(),
+            self.plan, C.byref(ds), self.nprob, p0, count, ndir, *self._lib4(), o["u"].data_ptr(), o["x"].data_ptr(),
             o["pi"].data_ptr(), o["lam"].data_ptr(), o["t"].data_ptr(), self.ws.data_ptr(),
             self.kkt_buffers(ndir)["scratch"].data_ptr(), compute_mult, self._stream()),
             "hpmpc_mi355x_ocp_tangent_batch")
@@ -405,7 +405,7 @@ class OcpBatchSolver:
         p0, count = self._range(p0, count)
         out = self.kkt_buffers(ndir)
         check(kkt_tangent_call(self.torch, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), None, self.N, self.nprob, p0,
-                               count, ndir, self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None, db, dq, dd,
+                               count, ndir, *self._lib4(ptr=False), db, dq, dd,
                                out, self.ws, compute_mult, self._stream()), "hpmpc_mi355x_kkt_tangent_batch")
         return out["ux"], out["pi"], out["lam"], out["t"]
 
@@ -437,14 +437,11 @@ class OcpBatchSolver:
         and t, inf_norm_res (nprob, 4), kk and status per problem.  Asynchronous: synchronise before reading."""
         p0, count = self._range(p0, count)
         check(lib().hpmpc_mi355x_ocp_finish_batch(
-            self.plan, self.nprob, p0, count, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
-            self.DCt.data_ptr() if self.sizes["DCt"] else None, self.d.data_ptr(), self.ux.data_ptr(),
-            self.pi.data_ptr(), self.lam.data_ptr(), self.t.data_ptr(), self.res.data_ptr(), self.u.data_ptr(),
-            self.x.data_ptr(), self.pi_out.data_ptr(), self.lam_out.data_ptr(), self.t_out.data_ptr(),
-            self.inf_norm_res.data_ptr(), self._stream()), "hpmpc_mi355x_ocp_finish_batch")
-        s = self.sizes
-        return dict(u=self.u[:, :s["u"]], x=self.x[:, :s["x"]], pi=self.pi_out[:, :s["pi_out"]],
-                    lam=self.lam_out[:, :s["lam_out"]], t=self.t_out[:, :s["lam_out"]],
+            self.plan, self.nprob, p0, count, *self._lib4(), self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(),
+            self.lam.data_ptr(), self.t.data_ptr(), self.res.data_ptr(), self.u.data_ptr(), self.x.data_ptr(),
+            self.pi_out.data_ptr(), self.lam_out.data_ptr(), self.t_out.data_ptr(), self.inf_norm_res.data_ptr(),
+            self._stream()), "hpmpc_mi355x_ocp_finish_batch")
+        return dict(self._sized(dict(u=self.u, x=self.x, pi=self.pi_out, lam=self.lam_out, t=self.t_out)),
                     inf_norm_res=self.inf_norm_res, kk=self.kk, status=self.ret)
 
     def results(self, out=None) -> list:

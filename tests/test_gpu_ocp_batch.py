@@ -318,3 +318,82 @@ def test_tile_plan_runs_the_existing_batched_call(refs):
                                   sg.lam.data_ptr(), sg.t.data_ptr(), sg.ws.data_ptr(), sg.k_max, 2.0, 1e-10, 1e-8, 0, 1,
                                   sg.kk.data_ptr(), sg.ret.data_ptr(), sg.stat.data_ptr(), sg._stream())
     assert rc == EUNSUPPORTED
+
+
+# --------------------------------------------------------------------------- 11, 12: one placement for every unpack / pack
+@pytest.mark.parametrize("order", ["C", "F"])
+def test_finish_equals_the_one_set_unpack(order):
+    """hpmpc_mi355x_ocp_finish_batch and hpmpc_mi355x_ocp_unpack_sets(nrhs = 1) run one kernel: on the solver's own d,
+    ux, pi, lam, t they give the same u, x (equality-box fix included), pi, lam, t bit for bit, and neither writes t
+    when t_out is null."""
+    L = ocp_lib()
+    Ps = problems("V", range(4))
+    P = Ps[1]
+    P["ub"][0] = P["ub"][0].copy()
+    P["ub"][0][0] = P["lb"][0][0]  # input box 0 of stage 0: lb == ub
+    j = int(P["hidxb"][0][0])
+    assert j < P["nu"][0]
+    sv = make_solver(Ps, order)
+    pack_problems(sv, Ps)
+    sv.solve(**ARGS)
+    torch, s = sv.torch, sv.sizes
+    names = (("u", "u"), ("x", "x"), ("pi", "pi_out"), ("lam", "lam_out"), ("t", "lam_out"))
+    fin = {k: v.clone() for k, v in sv.finish().items()}
+    assert fin["u"][1, sv.offsets["r"][0] + j].item() == P["lb"][0][0]
+    new = lambda: {k: torch.full((sv.nprob, max(s[n], 1)), SENTINEL, dtype=torch.float64, device=sv.dev)
+                   for k, n in names}
+    ptr = lambda x: x.data_ptr()
+    padded = [ptr(x) for x in (sv.d, sv.ux, sv.pi, sv.lam, sv.t)]
+
+    def unpack(o, t=True):
+        return L.hpmpc_mi355x_ocp_unpack_sets(sv.plan, sv.nprob, 0, sv.nprob, 1, *padded, ptr(o["u"]), ptr(o["x"]),
+                                              ptr(o["pi"]), ptr(o["lam"]), ptr(o["t"]) if t else None, sv._stream())
+
+    def finish(o, t=True):
+        return L.hpmpc_mi355x_ocp_finish_batch(sv.plan, sv.nprob, 0, sv.nprob, ptr(sv.BAbt), ptr(sv.RSQrq), ptr(sv.DCt),
+                                               *padded, ptr(sv.res), ptr(o["u"]), ptr(o["x"]), ptr(o["pi"]),
+                                               ptr(o["lam"]), ptr(o["t"]) if t else None, ptr(sv.inf_norm_res),
+                                               sv._stream())
+
+    for call in (unpack, finish):
+        for with_t in (True, False):
+            o = new()
+            assert call(o, with_t) == 0, (call.__name__, with_t)
+            torch.cuda.synchronize()
+            for k, n in names:
+                got = o[k][:, :s[n]].cpu().numpy()
+                if k == "t" and not with_t:
+                    assert bool((o[k] == SENTINEL).all()), call.__name__
+                else:
+                    assert s[n] > 0 and np.array_equal(_bits(got), _bits(fin[k].cpu().numpy())), (call.__name__, k)
+                assert bool((o[k][:, s[n]:] == SENTINEL).all())
+
+
+def test_pack_vectors_tail_group():
+    """Three stages: the four-stages-per-workgroup group of hk_ocp_pack_vectors has one idle wave.  On NaN-prefilled
+    arrays after a full pack, pack(matrices=False) writes exactly the b row, the r / q row and d."""
+    Ps = problems("R", range(5))
+    sv = make_solver(Ps, "C")
+    pack_problems(sv, Ps)
+    full = packed_host(sv)
+    for x in (sv.BAbt, sv.RSQrq, sv.d):
+        x.fill_(float("nan"))
+    pack_problems(sv, Ps, matrices=False)
+    got = packed_host(sv)
+    for p, P in enumerate(Ps):
+        want = expected_packed(sv, P)
+        assert np.array_equal(full["d"][p], want["d"])
+        assert np.array_equal(_bits(got["d"][p]), _bits(want["d"]))
+        rows = {name: np.zeros(want[name].size, dtype=bool) for name in ("BAbt", "RSQrq")}
+        for k in range(P["N"] + 1):
+            nux, nx1 = P["nu"][k] + P["nx"][k], (P["nx"][k + 1] if k < P["N"] else 0)
+            row = lambda sd, i: (nux // 4) * 4 * sd + nux % 4 + 4 * i
+            for i in range(nx1):
+                rows["BAbt"][sv.offsets["BAbt"][k] + row((nx1 + 1) // 2 * 2, i)] = True
+            for i in range(nux):
+                rows["RSQrq"][sv.offsets["RSQrq"][k] + row((nux + 1) // 2 * 2, i)] = True
+        for name, m in rows.items():
+            assert m.any() and not m.all()
+            assert np.array_equal(full[name][p], want[name]), (p, name)
+            assert np.array_equal(_bits(got[name][p][m]), _bits(want[name][m])), (p, name)
+            assert np.isnan(got[name][p][~m]).all(), (p, name)  # nothing else is written

@@ -24,8 +24,8 @@ def test_entry_points_are_declared_and_bound():
     # the core call has the re-solve's argument list, the dense one an OCP plan and a direction struct in front
     assert want[NEW[0]] == want["hpmpc_mi355x_kkt_new_rhs_batch"]
     assert len(want[NEW[1]][1]) == 18 and len(want[NEW[2]][1]) == 16
-    assert "hk_tan.hip" in build.SOURCES and "hpmpc_capi_tan.cpp" in build.SOURCES
-    assert {"hk_tan_args.h", "hk_tan_body.h", "hk_ocp_plan.h"} <= set(build.HEADERS)
+    assert "hk_tan.hip" in build.SOURCES and "hpmpc_capi_kkt.cpp" in build.SOURCES  # the tangent's host entry points
+    assert {"hk_tan_args.h", "hk_tan_body.h", "hk_ocp_plan.h", "hk_ocp_place.h", "hk_kkt_launch.h"} <= set(build.HEADERS)
     assert "hk_tan.hip" in build.SRC_FLAGS
 
 

@@ -3,9 +3,8 @@ against the one-problem entry point that was the only route to a re-solve before
 
     python tools/kkt_batch_time.py [--nprob 1024] [--distinct 64] [--base 64] [--warmup 3] [--runs 10] [--out FILE.json]
 
-Batch: `nprob` problems of N=100, nx=12, nu=4 (nx[0] = 0) with 4 input and 6 state boxes per stage, from
-oracle/iface_oracle.py random_iface_problem; `distinct` different problems are generated and tiled to the batch (every
-problem and every right-hand-side set still has its own arrays in HBM).
+Batch: that of tools/batch_time.py (`nprob` problems, `distinct` different ones tiled to the batch; every problem and
+every right-hand-side set still has its own arrays in HBM).
   solve            : hpmpc_mi355x_ocp_ipm_batch on the batch, hipEvents around the call, `warmup` runs, then the
                      median of `runs`; it leaves the factor the re-solves use;
   resolve nrhs=1,8 : OcpBatchSolver.kkt_sets with explicit b, q, d (IO.new_rhs of each problem), timed the same way;
@@ -17,33 +16,15 @@ problem and every right-hand-side set still has its own arrays in HBM).
 Prints one JSON line.
 """
 import argparse
-import json
 import os
 import sys
 import time
 
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
+from batch_time import ARGS, CASE, emit, tiled_batch, timed  # noqa: E402
 
-N, NX, NU, NBU, NBX = 100, 12, 4, 4, 6
-ARGS = dict(mu0=2.0, mu_tol=1e-10, alpha_min=1e-8)
 NRHS = (1, 8)
-
-
-def timed(torch, fn, warmup, runs):
-    ms = []
-    for i in range(warmup + runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ms.append(e0.elapsed_time(e1))
-    return dict(ms=float(np.median(ms)), ms_min=float(min(ms)), ms_max=float(max(ms)))
 
 
 def set_bytes(sv):
@@ -85,17 +66,11 @@ def main():
     import torch
 
     import iface_oracle as IO
-    from hpmpc_amd.ocp_batch import OcpBatchSolver, flatten_problems, kkt_set_arrays
+    from hpmpc_amd.ocp_batch import kkt_set_arrays
 
-    nd = min(a.distinct, a.nprob)
-    Ps = [IO.random_iface_problem(N, [0] + [NX] * N, [NU] * N, NBU, NBX, None, seed=1000 + s) for s in range(nd)]
-    P0 = Ps[0]
-    sv = OcpBatchSolver(N, P0["nx"], P0["nu"], P0["nb"], P0["hidxb"], P0["ng"], a.nprob, order="C", k_max=50)
-    flat = flatten_problems(Ps, "C")
-    reps = -(-a.nprob // nd)
-    tile = lambda v: np.tile(v, (reps,) + (1,) * (v.ndim - 1))[:a.nprob].copy()
-    sv.pack({k: torch.from_numpy(tile(v)).to(sv.dev) for k, v in flat.items()})
-    out = dict(case=f"random_iface_problem N={N} nx={NX} nu={NU} boxes {NBU}+{NBX}", nprob=a.nprob, distinct=nd,
+    Ps, nd, sv, tile, data = tiled_batch(torch, a.nprob, a.distinct)
+    sv.pack(data)
+    out = dict(case=CASE, nprob=a.nprob, distinct=nd,
                args=ARGS, runs=a.runs, warmup=a.warmup, bytes_per_set=set_bytes(sv))
     out["solve"] = timed(torch, lambda: sv.solve(**ARGS), a.warmup, a.runs)
     kk, ret = sv.kk.cpu().numpy(), sv.ret.cpu().numpy()
@@ -119,12 +94,7 @@ def main():
     out["part1_loop"] = dict(problems=nb, ms_measured=ms, scale=a.nprob / nb, ms_scaled=ms * a.nprob / nb,
                              label="scaled from %d problems, not measured on the batch" % nb)
     out["part1_over_resolve_nrhs1"] = out["part1_loop"]["ms_scaled"] / out["resolve_nrhs1"]["ms"]
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, a.out)
 
 
 if __name__ == "__main__":

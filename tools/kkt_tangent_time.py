@@ -3,31 +3,30 @@ beside the re-solve it is the linear part of (hpmpc_mi355x_kkt_new_rhs_batch, hk
 
     python tools/kkt_tangent_time.py [--nprob 1024] [--distinct 64] [--warmup 3] [--runs 10] [--out FILE.json]
 
-Batch: that of tools/kkt_batch_time.py -- `nprob` problems of N=100, nx=12, nu=4 (nx[0] = 0) with 4 input and 6 state
-boxes per stage, `distinct` different problems tiled to the batch (every problem and every set still has its own
-arrays in HBM).  One hpmpc_mi355x_ocp_ipm_batch leaves the factor.  Then, for ndir = 1, 8, 12 sets per problem:
+Batch: that of tools/batch_time.py (`nprob` problems, `distinct` different ones tiled to the batch; every problem and
+every set still has its own arrays in HBM).  One hpmpc_mi355x_ocp_ipm_batch leaves the factor.  Then, for ndir = 1, 8,
+12 sets per problem:
   resolve : OcpBatchSolver.kkt_sets with explicit b, q, d (IO.new_rhs of each problem), hk_kkt_rhs;
+  resolve_dense : the same with dense=True, so with the multi-set finish (hk_ocp_unpack) after it: the finish's cost
+            is this leg minus `resolve`;
   tangent : OcpBatchSolver.tangent_sets with the directions new_rhs - problem (padded arrays), hk_kkt_tan;
   dense   : OcpBatchSolver.tangent with the same directions as dense tensors (the same kernel with its dense prologue
             and epilogue).
-hipEvents around each call; per run the three are called one after another (alternated in one process, so that clock
+hipEvents around each call; per run the four are called one after another (alternated in one process, so that clock
 and thermal drift hit them alike), `warmup` such rounds, then the median, minimum and maximum of `runs`.  us per set
 and GB/s against the bytes a set must move (its problem's BAbt, RSQrq and factor once, its vectors in and out;
 work-vector traffic not counted).  Prints one JSON line.
 """
 import argparse
-import json
 import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from kkt_batch_time import ARGS, N, NBU, NBX, NU, NX, set_bytes  # noqa: E402
+from batch_time import ARGS, CASE, alternated, emit, tiled_batch  # noqa: E402
+from kkt_batch_time import set_bytes  # noqa: E402
 
 NDIR = (1, 8, 12)
 VEC_KEYS = ("b", "q", "r", "lb", "ub", "lg", "ug")
@@ -42,21 +41,6 @@ def tangent_bytes(sv):
                 (2 * 16 + 2 * 32) * n1)
 
 
-def alternated(torch, fns, warmup, runs):
-    """{name: timing}: each round calls every function once, in order, with its own pair of events."""
-    ms = {name: [] for name in fns}
-    for i in range(warmup + runs):
-        for name, fn in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            torch.cuda.synchronize()
-            if i >= warmup:
-                ms[name].append(e0.elapsed_time(e1))
-    return {name: dict(ms=float(np.median(v)), ms_min=float(min(v)), ms_max=float(max(v))) for name, v in ms.items()}
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nprob", type=int, default=1024)
@@ -68,20 +52,15 @@ def main():
     import torch
 
     import iface_oracle as IO
-    from hpmpc_amd.ocp_batch import OcpBatchSolver, flatten_problems, kkt_set_arrays, tangent_set_arrays
+    from hpmpc_amd.ocp_batch import kkt_set_arrays, tangent_set_arrays
 
-    nd = min(a.distinct, a.nprob)
-    Ps = [IO.random_iface_problem(N, [0] + [NX] * N, [NU] * N, NBU, NBX, None, seed=1000 + s) for s in range(nd)]
+    Ps, nd, sv, tile, data = tiled_batch(torch, a.nprob, a.distinct)
     P0 = Ps[0]
-    sv = OcpBatchSolver(N, P0["nx"], P0["nu"], P0["nb"], P0["hidxb"], P0["ng"], a.nprob, order="C", k_max=50)
-    flat = flatten_problems(Ps, "C")
-    reps = -(-a.nprob // nd)
-    tile = lambda v: np.tile(v, (reps,) + (1,) * (v.ndim - 1))[:a.nprob].copy()
-    sv.pack({k: torch.from_numpy(tile(v)).to(sv.dev) for k, v in flat.items()})
+    sv.pack(data)
     sv.solve(**ARGS)
     torch.cuda.synchronize()
     kk, ret = sv.kk.cpu().numpy(), sv.ret.cpu().numpy()
-    out = dict(case=f"random_iface_problem N={N} nx={NX} nu={NU} boxes {NBU}+{NBX}", nprob=a.nprob, distinct=nd,
+    out = dict(case=CASE, nprob=a.nprob, distinct=nd,
                args=ARGS, runs=a.runs, warmup=a.warmup, bytes_per_set=dict(resolve=set_bytes(sv), tangent=tangent_bytes(sv)),
                solve=dict(kk_min=int(kk.min()), kk_max=int(kk.max()), ret_nonzero=int((ret != 0).sum())))
     sets = [[IO.new_rhs(P, seed=6 + r) for r in range(max(NDIR))] for P in Ps]
@@ -98,27 +77,24 @@ def main():
                              for row in deltas]).reshape(nd, ndir, -1)
             dirs[key] = torch.from_numpy(tile(rows)).to(sv.dev)
         t = alternated(torch, dict(resolve=lambda: sv.kkt_sets(b, q, d, nrhs=ndir),
+                                   resolve_dense=lambda: sv.kkt_sets(b, q, d, nrhs=ndir, dense=True),
                                    tangent=lambda: sv.tangent_sets(db, dq, dd, ndir),
                                    dense=lambda: sv.tangent(dirs, ndir)), a.warmup, a.runs)
         nsets = a.nprob * ndir
         for name, r in t.items():
-            nbytes = out["bytes_per_set"]["resolve" if name == "resolve" else "tangent"]
+            nbytes = out["bytes_per_set"]["resolve" if name.startswith("resolve") else "tangent"]
             r.update(us_per_set=r["ms"] * 1e3 / nsets, GBps=nbytes * nsets / (r["ms"] * 1e-3) / 1e9)
         t["sets"] = nsets
         t["tangent_over_resolve"] = t["tangent"]["ms"] / t["resolve"]["ms"]
         t["dense_over_resolve"] = t["dense"]["ms"] / t["resolve"]["ms"]
+        t["unpack_sets_ms"] = t["resolve_dense"]["ms"] - t["resolve"]["ms"]
         # per-set excess of the tangent over the re-solve against the runs' own min-max spread (us per set)
         t["excess_us_per_set"] = (t["tangent"]["ms"] - t["resolve"]["ms"]) * 1e3 / nsets
         t["spread_us_per_set"] = max(r["ms_max"] - r["ms_min"] for r in (t["tangent"], t["resolve"])) * 1e3 / nsets
         t["finite"] = bool(torch.isfinite(sv.set_buffers(ndir)["x"]).all().item())
         out[f"ndir{ndir}"] = t
         del b, q, d, db, dq, dd, dirs
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, a.out)
 
 
 if __name__ == "__main__":

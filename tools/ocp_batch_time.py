@@ -1,11 +1,9 @@
-"""Time the batched OCP front end (hpmpc_amd/ocp_batch.py: hk_ocp_pack, the IPM, hk_res + hk_ocp_finish) against
+"""Time the batched OCP front end (hpmpc_amd/ocp_batch.py: hk_ocp_pack, the IPM, hk_res + hk_ocp_unpack) against
 the host packing route that was the only one before it.
 
     python tools/ocp_batch_time.py [--nprob 1024] [--distinct 64] [--base 64] [--warmup 3] [--runs 10] [--out FILE.json]
 
-Batch: `nprob` problems of N=100, nx=12, nu=4 (nx[0] = 0) with 4 input and 6 state boxes per stage, from
-oracle/iface_oracle.py random_iface_problem; `distinct` different problems are generated and tiled to the batch (every
-problem still has its own copy of every array in HBM, so the bytes moved are those of `nprob` different problems).
+Batch: that of tools/batch_time.py (`nprob` problems, `distinct` different ones tiled to the batch).
   pack, pack (matrices=0), finish, solve : hipEvents around the call, `warmup` runs, then the median of `runs`;
   TB/s                                   : against the bytes the call must read plus write (algorithmic: every dense
                                            input once, every output element once; for finish the two kernels' inputs
@@ -16,32 +14,15 @@ problem still has its own copy of every array in HBM, so the bytes moved are tho
 Prints one JSON line.
 """
 import argparse
-import json
 import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-N, NX, NU, NBU, NBX = 100, 12, 4, 4, 6
-ARGS = dict(mu0=2.0, mu_tol=1e-10, alpha_min=1e-8)
-
-
-def timed(torch, fn, warmup, runs):
-    ms = []
-    for i in range(warmup + runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ms.append(e0.elapsed_time(e1))
-    return dict(ms=float(np.median(ms)), ms_min=float(min(ms)), ms_max=float(max(ms)))
+from batch_time import ARGS, CASE, emit, tiled_batch, timed  # noqa: E402
 
 
 def byte_counts(sv):
@@ -88,18 +69,9 @@ def main():
     a = ap.parse_args()
     import torch
 
-    import iface_oracle as IO
-    from hpmpc_amd.ocp_batch import OcpBatchSolver, flatten_problems
-
-    nd = min(a.distinct, a.nprob)
-    Ps = [IO.random_iface_problem(N, [0] + [NX] * N, [NU] * N, NBU, NBX, None, seed=1000 + s) for s in range(nd)]
-    P0 = Ps[0]
-    sv = OcpBatchSolver(N, P0["nx"], P0["nu"], P0["nb"], P0["hidxb"], P0["ng"], a.nprob, order="C", k_max=50)
-    flat = flatten_problems(Ps, "C")
-    reps = -(-a.nprob // nd)
-    data = {k: torch.from_numpy(np.tile(v, (reps, 1))[:a.nprob].copy()).to(sv.dev) for k, v in flat.items()}
+    Ps, nd, sv, _, data = tiled_batch(torch, a.nprob, a.distinct)
     nbytes = byte_counts(sv)
-    out = dict(case=f"random_iface_problem N={N} nx={NX} nu={NU} boxes {NBU}+{NBX}", nprob=a.nprob, distinct=nd,
+    out = dict(case=CASE, nprob=a.nprob, distinct=nd,
                order="C", args=ARGS, runs=a.runs, warmup=a.warmup, bytes_per_problem=nbytes)
 
     def rate(t, key):
@@ -130,12 +102,7 @@ def main():
                              label="scaled from %d problems, not measured on the batch" % nb,
                              same_arrays_as_hk_ocp_pack=same)
     out["host_route_over_pack"] = out["host_route"]["ms_scaled"] / out["pack"]["ms"]
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, a.out)
 
 
 if __name__ == "__main__":
