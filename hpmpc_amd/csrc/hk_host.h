@@ -8,6 +8,7 @@
 
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "hpmpc_api.h"
 #include "hk_launch.h"
@@ -18,7 +19,8 @@ extern thread_local int g_err;
 extern "C" {
 // hpmpc_capi.cpp: records the code and, when it is nonzero, prints one stderr line; code 0 clears the error
 void hk_set_error(int code, const char* what);
-// hpmpc_capi_wide.cpp: the drop-in Riccati entry points on stages beyond the 16-wide tile
+// hpmpc_capi_wide.cpp: the drop-in Riccati entry points on stages beyond the 16-wide tile (partial condensing on the
+// same stages is hpmpc_capi_pcond.cpp; its entry points are public, include/hpmpc_mi355x.h)
 long long hk_wide_factor_bytes(int N, const int* nx, const int* nu);
 void hk_wide_sv_entry(int N, int* nx, int* nu, int* nb, int** idxb, int* ng, int update_b, double** hpBAbt,
                       double** b, int update_q, double** hpQ, double** q, double** bd, double** hpDCt, double** Qx,
@@ -48,7 +50,9 @@ void hk_wide_res_entry(int plain, int N, int* nx, int* nu, int* nb, int** idxb, 
 constexpr int BS = 4, NCL = 2;  // lib4: panel height, column-count granule of the panel stride
 
 inline int rup(int n, int m) { return (n + m - 1) / m * m; }
-inline double& P4(double* A, int sd, int i, int j) { return A[(i / BS) * BS * sd + i % BS + BS * j]; }
+// element (i, j) of a lib4 matrix with panel stride sd
+inline long long idx4(int sd, int i, int j) { return (long long)(i / BS) * BS * sd + i % BS + BS * j; }
+inline double& P4(double* A, int sd, int i, int j) { return A[idx4(sd, i, j)]; }
 
 inline bool hip_ok(hipError_t e, const char* what) {
     if (e == hipSuccess) return true;
@@ -57,6 +61,26 @@ inline bool hip_ok(hipError_t e, const char* what) {
     hk_set_error(HPMPC_MI355X_EHIP, msg);
     return false;
 }
+
+// The device copy of a host array: allocated and filled by upload(), freed with its owner, never rewritten.
+template <class T>
+class DevTable {
+    T* d_ = nullptr;
+
+public:
+    DevTable() = default;
+    DevTable(DevTable&& o) noexcept : d_(o.d_) { o.d_ = nullptr; }
+    DevTable(const DevTable&) = delete;
+    DevTable& operator=(const DevTable&) = delete;
+    ~DevTable() {
+        if (d_) (void)hipFree(d_);
+    }
+    bool upload(const std::vector<T>& h, const char* what) {
+        return hip_ok(hipMalloc((void**)&d_, sizeof(T) * h.size()), what) &&
+               hip_ok(hipMemcpy(d_, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice), what);
+    }
+    const T* get() const { return d_; }
+};
 
 // The device context of the host-buffer entry points, one per host thread (g_dev, defined in hpmpc_capi.cpp): a
 // stream, a device arena and its pinned staging twin, sized in bytes and only ever grown.  Nothing in the arenas

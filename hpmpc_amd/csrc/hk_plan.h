@@ -18,26 +18,6 @@ struct StageInfoH {  // mirror of hk::StageInfo
     int nu, nx, nb, ng, xo, nx1, nu1, xo1, sdB, sdR, oB, oR, oD, pnb, r0, oG;
 };
 
-// The device copy of a host array: allocated and filled by upload(), freed with its owner, never rewritten.
-template <class T>
-class DevTable {
-    T* d_ = nullptr;
-
-public:
-    DevTable() = default;
-    DevTable(DevTable&& o) noexcept : d_(o.d_) { o.d_ = nullptr; }
-    DevTable(const DevTable&) = delete;
-    DevTable& operator=(const DevTable&) = delete;
-    ~DevTable() {
-        if (d_) (void)hipFree(d_);
-    }
-    bool upload(const std::vector<T>& h, const char* what) {
-        return hip_ok(hipMalloc((void**)&d_, sizeof(T) * h.size()), what) &&
-               hip_ok(hipMemcpy(d_, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice), what);
-    }
-    const T* get() const { return d_; }
-};
-
 // Plan: stage tables shared by every problem of a batch.
 struct hpmpc_mi355x_plan {
     int N = 0;

@@ -1,6 +1,8 @@
-// hk_wide_host.h -- host-side helpers of the wide-stage path shared by hpmpc_capi_wide.cpp (Riccati, condensing)
-// and hpmpc_capi_wide_ipm.cpp (the IPM on wide stages): the packed per-problem layout of a wide problem, the byte
-// carve of the staging arena (the thread's device context, g_dev of hk_host.h) and the launch wrapper.
+// hk_wide_host.h -- host-side helpers of the wide-stage path shared by hpmpc_capi_wide.cpp (Riccati),
+// hpmpc_capi_pcond.cpp (partial condensing, through hk_pcond_plan.h) and hpmpc_capi_wide_ipm.cpp (the IPM on wide
+// stages): the packed per-problem layout of a wide problem, the WideArgs fields that follow from it, the typed carve
+// of the staging arena (the thread's device context, g_dev of hk_host.h), the copies between the caller's per-stage
+// buffers and the packed layout, and the launch wrapper.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -14,6 +16,13 @@ namespace {
 constexpr int LDS_MAX_DOUBLES = 65536 / 8;
 
 inline int poff(int j, int nz) { return j * nz - (j * (j - 1)) / 2; }
+
+// Lengths (doubles) of stage k's lib4 blocks BAbt_k / RSQrq_k / DCt_k and of its constraint vector
+// [lb | ub | lg | ug] (d, lam, t and their kin).
+inline size_t len_BAbt(const WideStage& s) { return (size_t)rup(s.nu + s.nx + 1, BS) * s.sdB; }
+inline size_t len_RSQ(const WideStage& s) { return (size_t)rup(s.nu + s.nx + 1, BS) * s.sdR; }
+inline size_t len_DCt(const WideStage& s) { return (size_t)rup(s.nu + s.nx, BS) * s.sdG; }
+inline int len_cvec(const WideStage& s) { return 2 * s.pnb + 2 * rup(s.ng, BS); }
 
 // One problem's packed layout on the wide path (offsets in doubles; idxb in ints).
 struct WLayout {
@@ -40,10 +49,14 @@ WLayout make_layout(int N, const int* nx, const int* nu, const int* nb, const in
         const int nux = s.nu + s.nx;
         s.sdB = rup(s.nx1, NCL);
         s.sdR = rup(nux, NCL);
+        s.nb = nb[k];
+        s.pnb = rup(nb[k], BS);
+        s.ng = ng[k];
+        s.sdG = rup(ng[k], NCL);
         s.oB = (int)L.nB;
-        if (k < N) L.nB += (long long)rup(nux + 1, BS) * s.sdB;
+        if (k < N) L.nB += len_BAbt(s);
         s.oR = (int)L.nR;
-        L.nR += (long long)rup(nux + 1, BS) * s.sdR;
+        L.nR += len_RSQ(s);
         s.oL = (int)L.nL;
         L.nL += poff(nux, nux + 1) + nux;
         L.nL = (L.nL + 7) / 8 * 8;
@@ -51,14 +64,10 @@ WLayout make_layout(int N, const int* nx, const int* nu, const int* nb, const in
         L.nU += rup(nux + 1, 8);
         s.oP = (int)L.nP;
         L.nP += rup(s.nx1 + 1, 8);
-        s.nb = nb[k];
-        s.pnb = rup(nb[k], BS);
-        s.ng = ng[k];
-        s.sdG = rup(ng[k], NCL);
         s.oG = (int)L.nG;
-        L.nG += (long long)rup(nux, BS) * s.sdG;
+        L.nG += len_DCt(s);
         s.oD = (int)L.nD;
-        L.nD += 2 * s.pnb + 2 * rup(ng[k], BS);
+        L.nD += len_cvec(s);
         s.oI = (int)L.nI;
         L.nI += nb[k];
         if (ng[k] > 0) L.any_ng = true;
@@ -81,15 +90,85 @@ WLayout make_layout(int N, const int* nx, const int* nu, const int* nb, const in
     return L;
 }
 
-// Byte carve of the staging arena.
-struct Carve {
-    size_t o = 0;
-    size_t take(size_t bytes) {
-        size_t r = o;
-        o += (bytes + 255) / 256 * 256;
-        return r;
+// The sizes, per-problem strides and LDS carve of a zeroed WideArgs.
+inline void wide_args(const WLayout& L, int nprob, int p0, WideArgs& a) {
+    a.N = L.N;
+    a.nprob = nprob;
+    a.p0 = p0;
+    a.sB = L.nB;
+    a.sR = L.nR;
+    a.sW = L.nL;
+    a.sU = L.nU;
+    a.sP = L.nP;
+    a.sC = L.nD;
+    a.sG = L.nG;
+    a.offW = L.offW;
+    a.offX = L.offX;
+    a.offV = L.offV;
+    a.offST = L.offST;
+    a.ldW = L.ldW;
+    a.ldX = L.ldX;
+}
+
+// The staging arena of one call: n elements of T at the same offset of g_dev's pinned arena (host(), staged and
+// read back there) and of its device twin (dev(), what the argument block points to).  Every slot starts on a
+// 256-byte boundary; the pointers are valid once g_dev.ensure(Carve::o) has sized the arenas.
+template <class T>
+struct Slot {
+    size_t off = 0;
+    T* host() const { return reinterpret_cast<T*>(g_dev.host + off); }
+    T* dev() const { return reinterpret_cast<T*>(g_dev.dev + off); }
+    void put(const std::vector<T>& v) const {
+        if (!v.empty()) memcpy(host(), v.data(), sizeof(T) * v.size());
     }
 };
+struct Carve {
+    size_t o = 0;
+    template <class T>
+    Slot<T> take(size_t n) {
+        Slot<T> s{o};
+        o += (n * sizeof(T) + 255) / 256 * 256;
+        return s;
+    }
+};
+
+// The caller's per-stage buffers (lib4 blocks, possibly aliased stage pointers) into the packed layout ...
+inline void BAbt_in(const WLayout& L, double* H, double* const* p) {
+    for (int k = 0; k < L.N; k++) memcpy(H + L.st[k].oB, p[k], len_BAbt(L.st[k]) * sizeof(double));
+}
+inline void RSQ_in(const WLayout& L, double* H, double* const* p) {
+    for (int k = 0; k <= L.N; k++) memcpy(H + L.st[k].oR, p[k], len_RSQ(L.st[k]) * sizeof(double));
+}
+inline void DCt_in(const WLayout& L, double* H, double* const* p) {  // stages with ng > 0
+    for (int k = 0; k <= L.N; k++)
+        if (L.st[k].ng > 0) memcpy(H + L.st[k].oG, p[k], len_DCt(L.st[k]) * sizeof(double));
+}
+inline void idxb_in(const WLayout& L, int* H, int* const* idxb) {  // stages with nb > 0
+    for (int k = 0; k <= L.N; k++)
+        if (L.st[k].nb > 0) memcpy(H + L.st[k].oI, idxb[k], L.st[k].nb * sizeof(int));
+}
+// ... and the per-stage vectors in and out: ux_k (nu + nx), pi_k (nx_{k+1}, k < N), constraint vectors (stages with
+// nb + ng > 0; a null v stages nothing)
+inline void uvec_in(const WLayout& L, double* H, double* const* v) {
+    for (int k = 0; k <= L.N; k++) memcpy(H + L.st[k].oU, v[k], (L.st[k].nu + L.st[k].nx) * sizeof(double));
+}
+inline void uvec_out(const WLayout& L, const double* H, double* const* v) {
+    for (int k = 0; k <= L.N; k++) memcpy(v[k], H + L.st[k].oU, (L.st[k].nu + L.st[k].nx) * sizeof(double));
+}
+inline void pvec_in(const WLayout& L, double* H, double* const* v) {
+    for (int k = 0; k < L.N; k++) memcpy(H + L.st[k].oP, v[k], L.st[k].nx1 * sizeof(double));
+}
+inline void pvec_out(const WLayout& L, const double* H, double* const* v) {
+    for (int k = 0; k < L.N; k++) memcpy(v[k], H + L.st[k].oP, L.st[k].nx1 * sizeof(double));
+}
+inline void cvec_in(const WLayout& L, double* H, double* const* v) {
+    for (int k = 0; v && k <= L.N; k++)
+        if (L.st[k].nb + L.st[k].ng > 0) memcpy(H + L.st[k].oD, v[k], len_cvec(L.st[k]) * sizeof(double));
+}
+inline void cvec_out(const WLayout& L, const double* H, double* const* v) {
+    for (int k = 0; k <= L.N; k++)
+        if (L.st[k].nb + L.st[k].ng > 0) memcpy(v[k], H + L.st[k].oD, len_cvec(L.st[k]) * sizeof(double));
+}
 
 bool launch(int which, const void* args, int count, int lds, hipStream_t stream, const char* name) {
     if (lds > LDS_MAX_DOUBLES) {

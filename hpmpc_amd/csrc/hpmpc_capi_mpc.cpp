@@ -41,8 +41,6 @@
 
 namespace {
 
-inline long li(int sd, int i, int j) { return (long)(i / BS) * BS * sd + i % BS + BS * j; }
-
 struct Mpc {
     int N, nx, nu, nb, ng, ngN, nbu;
     bool ti, rowmajor;
@@ -194,14 +192,14 @@ void pack(Mpc& P, const Data& X, bool kkt) {
     }
     stage0_rhs(P, X, P.b[0], r0.data());
     for (int i = 0; i < nu; i++)  // B0' (the KKT wrapper restores it over the IPM's data, :3264)
-        for (int j = 0; j < nx; j++) P.BAbt[0][li(cnx, i, j)] = P.el(X.B, nx, nu, 0, j, i);
+        for (int j = 0; j < nx; j++) P.BAbt[0][idx4(cnx, i, j)] = P.el(X.B, nx, nu, 0, j, i);
     if (kkt) {
         for (int i = 0; i < nu; i++) P.rq[0][i] = r0[i];
     } else {
-        for (int j = 0; j < nx; j++) P.BAbt[0][li(cnx, nu, j)] = P.b[0][j];
+        for (int j = 0; j < nx; j++) P.BAbt[0][idx4(cnx, nu, j)] = P.b[0][j];
         for (int i = 0; i < nu; i++) {
-            for (int j = 0; j < nu; j++) P.RSQ[0][li(cnu, i, j)] = P.el(X.R, nu, nu, 0, i, j);
-            P.RSQ[0][li(cnu, nu, i)] = r0[i];
+            for (int j = 0; j < nu; j++) P.RSQ[0][idx4(cnu, i, j)] = P.el(X.R, nu, nu, 0, i, j);
+            P.RSQ[0][idx4(cnu, nu, i)] = r0[i];
         }
     }
     for (int k = 1; k < N; k++) {
@@ -214,39 +212,39 @@ void pack(Mpc& P, const Data& X, bool kkt) {
         }
         double* Bk = P.BAbt[k];
         for (int j = 0; j < nx; j++) {
-            for (int i = 0; i < nu; i++) Bk[li(cnx, i, j)] = P.el(X.B, nx, nu, k, j, i);
-            for (int i = 0; i < nx; i++) Bk[li(cnx, nu + i, j)] = P.el(X.A, nx, nx, k, j, i);
-            Bk[li(cnx, nu + nx, j)] = bk[j];
+            for (int i = 0; i < nu; i++) Bk[idx4(cnx, i, j)] = P.el(X.B, nx, nu, k, j, i);
+            for (int i = 0; i < nx; i++) Bk[idx4(cnx, nu + i, j)] = P.el(X.A, nx, nx, k, j, i);
+            Bk[idx4(cnx, nu + nx, j)] = bk[j];
         }
         double* Rk = P.RSQ[k];
         for (int i = 0; i < nu; i++) {
-            for (int j = 0; j < nu; j++) Rk[li(cnux, i, j)] = P.el(X.R, nu, nu, k, i, j);
-            Rk[li(cnux, nu + nx, i)] = rk[i];
+            for (int j = 0; j < nu; j++) Rk[idx4(cnux, i, j)] = P.el(X.R, nu, nu, k, i, j);
+            Rk[idx4(cnux, nu + nx, i)] = rk[i];
         }
         for (int i = 0; i < nx; i++) {
-            for (int j = 0; j < nu; j++) Rk[li(cnux, nu + i, j)] = P.el(X.S, nu, nx, k, j, i);
-            for (int j = 0; j < nx; j++) Rk[li(cnux, nu + i, nu + j)] = P.el(X.Q, nx, nx, k, i, j);
-            Rk[li(cnux, nu + nx, nu + i)] = qk[i];
+            for (int j = 0; j < nu; j++) Rk[idx4(cnux, nu + i, j)] = P.el(X.S, nu, nx, k, j, i);
+            for (int j = 0; j < nx; j++) Rk[idx4(cnux, nu + i, nu + j)] = P.el(X.Q, nx, nx, k, i, j);
+            Rk[idx4(cnux, nu + nx, nu + i)] = qk[i];
         }
     }
     if (kkt) {
         for (int i = 0; i < nx; i++) P.rq[N][i] = X.qf[i];
     } else {
         for (int i = 0; i < nx; i++) {
-            for (int j = 0; j < nx; j++) P.RSQ[N][li(cnx, i, j)] = P.el1(X.Qf, nx, nx, i, j);
-            P.RSQ[N][li(cnx, nx, i)] = X.qf[i];
+            for (int j = 0; j < nx; j++) P.RSQ[N][idx4(cnx, i, j)] = P.el1(X.Qf, nx, nx, i, j);
+            P.RSQ[N][idx4(cnx, nx, i)] = X.qf[i];
         }
         if (ng > 0)  // [D'; C'] (stage 0: D' only), :2592-2603
             for (int k = 0; k < N; k++) {
                 for (int i = 0; i < nu; i++)
-                    for (int j = 0; j < ng; j++) P.DCt[k][li(P.cng, i, j)] = P.el(X.D, ng, nu, k, j, i);
+                    for (int j = 0; j < ng; j++) P.DCt[k][idx4(P.cng, i, j)] = P.el(X.D, ng, nu, k, j, i);
                 if (k > 0)
                     for (int i = 0; i < nx; i++)
-                        for (int j = 0; j < ng; j++) P.DCt[k][li(P.cng, nu + i, j)] = P.el(X.C, ng, nx, k, j, i);
+                        for (int j = 0; j < ng; j++) P.DCt[k][idx4(P.cng, nu + i, j)] = P.el(X.C, ng, nx, k, j, i);
             }
         if (ngN > 0)
             for (int i = 0; i < nx; i++)
-                for (int j = 0; j < ngN; j++) P.DCt[N][li(P.cngN, i, j)] = P.el1(X.Cf, ngN, nx, j, i);
+                for (int j = 0; j < ngN; j++) P.DCt[N][idx4(P.cngN, i, j)] = P.el1(X.Cf, ngN, nx, j, i);
     }
     // bounds (:2683-2753)
     for (int k = 0; k < N; k++) {
@@ -259,8 +257,8 @@ void pack(Mpc& P, const Data& X, bool kkt) {
             } else {  // input equality constraint folded into b (:2695-2705), b row addressed as the reference does
                 for (int l = 0; l < nx; l++) {
                     const long row = (long)((P.nxx[k] + P.nuu[k]) / BS) * cnx * BS + (nx + nu) % BS + (long)l * BS;
-                    P.BAbt[k][row] += P.BAbt[k][li(cnx, i, l)] * lo;
-                    P.BAbt[k][li(cnx, i, l)] = 0.0;
+                    P.BAbt[k][row] += P.BAbt[k][idx4(cnx, i, l)] * lo;
+                    P.BAbt[k][idx4(cnx, i, l)] = 0.0;
                 }
                 P.d[k][i] = lo + 1e3;
                 P.d[k][i + p0] = up - 1e3;

@@ -115,109 +115,60 @@ bool ipm_check(const WIpm& W, int N, const int* nx, const int* nu, const int* nb
     return true;
 }
 
-// Device arena of one call (byte offsets) and the argument block.
+// Staging arena of one call.
+struct IpmCtl {  // what the kernel leaves for the host: kk, the return code, mu (residual routines: in / out)
+    int kk, ret;
+    double mu, pad[6];
+};
 struct Stage {
-    size_t oSt, oCs, oVb, oI, oB, oR, oG, oD, oU, oP, oLam, oT, ovb, ovq, oIW, oStat, oCtl, total;
+    Slot<WideStage> st;
+    Slot<WideCSlot> cs;
+    Slot<int> vbox, idxb;
+    Slot<double> B, R, G, d, ux, pi, lam, t, vb, vq, iw, stat;
+    Slot<IpmCtl> ctl;
+    size_t total;
 };
 
 Stage carve(const WIpm& W, int N, int k_max) {
     const WLayout& L = W.L;
     Carve c;
     Stage S;
-    S.oSt = c.take(sizeof(WideStage) * (N + 1));
-    S.oCs = c.take(sizeof(WideCSlot) * (W.cs.size() + 1));
-    S.oVb = c.take(sizeof(int) * L.nU);
-    S.oI = c.take(sizeof(int) * L.nI);
-    S.oB = c.take(8 * L.nB);
-    S.oR = c.take(8 * L.nR);
-    S.oG = c.take(8 * L.nG);
-    S.oD = c.take(8 * L.nD);
-    S.oU = c.take(8 * L.nU);
-    S.oP = c.take(8 * L.nP);
-    S.oLam = c.take(8 * L.nD);
-    S.oT = c.take(8 * L.nD);
-    S.ovb = c.take(8 * L.nP);
-    S.ovq = c.take(8 * L.nU);
-    S.oIW = c.take(8 * W.nIW);
-    S.oStat = c.take(8 * (5 * (size_t)(k_max > 0 ? k_max : 1) + 8));
-    S.oCtl = c.take(64);
+    S.st = c.take<WideStage>(N + 1);
+    S.cs = c.take<WideCSlot>(W.cs.size() + 1);
+    S.vbox = c.take<int>(L.nU);
+    S.idxb = c.take<int>(L.nI);
+    S.B = c.take<double>(L.nB);
+    S.R = c.take<double>(L.nR);
+    S.G = c.take<double>(L.nG);
+    S.d = c.take<double>(L.nD);
+    S.ux = c.take<double>(L.nU);
+    S.pi = c.take<double>(L.nP);
+    S.lam = c.take<double>(L.nD);
+    S.t = c.take<double>(L.nD);
+    S.vb = c.take<double>(L.nP);
+    S.vq = c.take<double>(L.nU);
+    S.iw = c.take<double>(W.nIW);
+    S.stat = c.take<double>(5 * (size_t)(k_max > 0 ? k_max : 1) + 8);
+    S.ctl = c.take<IpmCtl>(1);
     S.total = c.o;
     return S;
 }
 
-// stage the problem data (lib4 blocks, possibly aliased stage pointers) and the tables
-void stage_common(const WIpm& W, const Stage& S, char* H, int N, int** idxb, double** pBAbt, double** pQ,
-                  double** pDCt) {
-    const WLayout& L = W.L;
-    memcpy(H + S.oSt, L.st.data(), sizeof(WideStage) * (N + 1));
-    if (!W.cs.empty()) memcpy(H + S.oCs, W.cs.data(), sizeof(WideCSlot) * W.cs.size());
-    memcpy(H + S.oVb, W.vbox.data(), sizeof(int) * L.nU);
-    int* HI = reinterpret_cast<int*>(H + S.oI);
-    double* HB = reinterpret_cast<double*>(H + S.oB);
-    double* HR = reinterpret_cast<double*>(H + S.oR);
-    double* HG = reinterpret_cast<double*>(H + S.oG);
-    for (int k = 0; k <= N; k++) {
-        const WideStage& s = L.st[k];
-        const int nux = s.nu + s.nx;
-        memcpy(HR + s.oR, pQ[k], (size_t)rup(nux + 1, BS) * s.sdR * sizeof(double));
-        if (k < N) memcpy(HB + s.oB, pBAbt[k], (size_t)rup(nux + 1, BS) * s.sdB * sizeof(double));
-        if (s.ng > 0) memcpy(HG + s.oG, pDCt[k], (size_t)rup(nux, BS) * s.sdG * sizeof(double));
-        if (s.nb > 0) memcpy(HI + s.oI, idxb[k], s.nb * sizeof(int));
-    }
-}
-
-void cvec_in(const WIpm& W, const Stage& S, size_t off, char* H, int N, double** v) {
-    if (!v) return;
-    double* Hv = reinterpret_cast<double*>(H + off);
-    for (int k = 0; k <= N; k++) {
-        const WideStage& s = W.L.st[k];
-        const int n = 2 * s.pnb + 2 * rup(s.ng, BS);
-        if (s.nb + s.ng > 0) memcpy(Hv + s.oD, v[k], n * sizeof(double));
-    }
-}
-void cvec_out(const WIpm& W, const double* Hv, int N, double** v) {
-    for (int k = 0; k <= N; k++) {
-        const WideStage& s = W.L.st[k];
-        const int n = 2 * s.pnb + 2 * rup(s.ng, BS);
-        if (s.nb + s.ng > 0) memcpy(v[k], Hv + s.oD, n * sizeof(double));
-    }
-}
-void uvec_in(const WIpm& W, double* Hv, int N, double** v) {
-    for (int k = 0; k <= N; k++) memcpy(Hv + W.L.st[k].oU, v[k], (W.L.st[k].nu + W.L.st[k].nx) * sizeof(double));
-}
-void pvec_in(const WIpm& W, double* Hv, int N, double** v) {
-    for (int k = 0; k < N; k++) memcpy(Hv + W.L.st[k].oP, v[k], W.L.st[k].nx1 * sizeof(double));
-}
-
-void fill_args(const WIpm& W, const Stage& S, char* D, int N, WideIpmArgs& a) {
+// Everything in WideIpmArgs that follows from the work image, for problems [p0, ..) of nprob; the pointers are the
+// caller's: the one-problem arena (stage) or a batch's device arrays (hpmpc_mi355x_wide_ipm_batch).
+void ipm_args(const WIpm& W, int nprob, int p0, int k_max, WideIpmArgs& a) {
     const WLayout& L = W.L;
     memset(&a, 0, sizeof a);
-    a.w.N = N;
-    a.w.nprob = 1;
-    a.w.st = reinterpret_cast<const WideStage*>(D + S.oSt);
-    a.w.BAbt = reinterpret_cast<const double*>(D + S.oB);
-    a.w.RSQ = reinterpret_cast<const double*>(D + S.oR);
-    a.w.DCt = reinterpret_cast<const double*>(D + S.oG);
-    a.w.idxb = reinterpret_cast<const int*>(D + S.oI);
-    a.w.offW = L.offW;
-    a.w.offX = L.offX;
-    a.w.offV = L.offV;
-    a.w.offST = L.offST;
-    a.w.ldW = L.ldW;
-    a.w.ldX = L.ldX;
+    wide_args(L, nprob, p0, a.w);
+    a.k_max = k_max;
     a.mu_scal = W.nbt ? 1.0 / (2.0 * (double)W.nbt) : 0.0;
     a.nbt2 = 2.0 * (double)W.nbt;
     a.ncs = (int)W.cs.size();
-    a.cs = reinterpret_cast<const WideCSlot*>(D + S.oCs);
-    a.vbox = reinterpret_cast<const int*>(D + S.oVb);
     a.nU = (int)L.nU;
     a.nP = (int)L.nP;
-    a.d = reinterpret_cast<const double*>(D + S.oD);
-    a.ux = reinterpret_cast<double*>(D + S.oU);
-    a.pi = reinterpret_cast<double*>(D + S.oP);
-    a.lam = reinterpret_cast<double*>(D + S.oLam);
-    a.t = reinterpret_cast<double*>(D + S.oT);
-    a.iw = reinterpret_cast<double*>(D + S.oIW);
+    a.sC = L.nD;
+    a.sI = W.nIW;
+    a.sS = 5LL * (k_max > 0 ? k_max : 1);
     a.oF = W.oF;
     a.oDux = W.oDux;
     a.oDpi = W.oDpi;
@@ -228,24 +179,56 @@ void fill_args(const WIpm& W, const Stage& S, char* D, int N, WideIpmArgs& a) {
     a.oPib = W.oPib;
     int* oc[10] = {&a.oDlam, &a.oDt, &a.oTinv, &a.oLamt, &a.oRd, &a.oRm, &a.oTb, &a.oLb, &a.oQx, &a.oqx};
     for (int i = 0; i < 10; i++) *oc[i] = W.oC[i];
-    a.stat = reinterpret_cast<double*>(D + S.oStat);
-    a.kk = reinterpret_cast<int*>(D + S.oCtl);
-    a.ret = a.kk + 1;
-    a.mu = reinterpret_cast<double*>(D + S.oCtl + 8);
     a.offR = L.lds;
     a.offKC = L.lds + 8;
 }
 
+// one launch of hk_wide_ipm; 0, or the error code it set
+int ipm_launch(const WIpm& W, const WideIpmArgs& a, int count, hipStream_t stream) {
+    const int e = hk_wide_ipm_launch(&a, count, ipm_lds(W.L), stream);
+    if (!e) return 0;
+    char msg[96];
+    snprintf(msg, sizeof msg, "hk_wide_ipm launch %s (%d)", e == -2 ? "refused: scratch / LDS beyond the limits" : "failed", e);
+    const int code = e == -2 ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP;
+    hk_set_error(code, msg);
+    return code;
+}
+
+// stage the tables and the problem data (lib4 blocks, possibly aliased stage pointers) and point the one-problem
+// argument block at the arena
+void stage(const WIpm& W, const Stage& S, int k_max, int** idxb, double** pBAbt, double** pQ, double** pDCt, double** d,
+           WideIpmArgs& a) {
+    const WLayout& L = W.L;
+    S.st.put(L.st);
+    S.cs.put(W.cs);
+    S.vbox.put(W.vbox);
+    idxb_in(L, S.idxb.host(), idxb);
+    BAbt_in(L, S.B.host(), pBAbt);
+    RSQ_in(L, S.R.host(), pQ);
+    DCt_in(L, S.G.host(), pDCt);
+    cvec_in(L, S.d.host(), d);
+    ipm_args(W, 1, 0, k_max, a);
+    a.w.st = S.st.dev();
+    a.w.BAbt = S.B.dev();
+    a.w.RSQ = S.R.dev();
+    a.w.DCt = S.G.dev();
+    a.w.idxb = S.idxb.dev();
+    a.cs = S.cs.dev();
+    a.vbox = S.vbox.dev();
+    a.d = S.d.dev();
+    a.ux = S.ux.dev();
+    a.pi = S.pi.dev();
+    a.lam = S.lam.dev();
+    a.t = S.t.dev();
+    a.iw = S.iw.dev();
+    a.stat = S.stat.dev();
+    a.kk = &S.ctl.dev()->kk;
+    a.ret = &S.ctl.dev()->ret;
+    a.mu = &S.ctl.dev()->mu;
+}
+
 bool run(const WIpm& W, const Stage& S, const WideIpmArgs& a) {
-    if (!g_dev.up(S.total)) return false;
-    const int e = hk_wide_ipm_launch(&a, 1, ipm_lds(W.L), g_dev.stream);
-    if (e) {
-        char msg[96];
-        snprintf(msg, sizeof msg, "hk_wide_ipm launch %s (%d)", e == -2 ? "refused: scratch / LDS beyond the limits" : "failed", e);
-        hk_set_error(e == -2 ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP, msg);
-        return false;
-    }
-    return g_dev.down(S.total);
+    return g_dev.up(S.total) && !ipm_launch(W, a, 1, g_dev.stream) && g_dev.down(S.total);
 }
 
 }  // namespace
@@ -267,6 +250,7 @@ extern "C" int hk_wide_ipm_entry(int mode, int* kk, int k_max, double mu0, doubl
     std::vector<int> nu(nu_N, nu_N + N + 1);
     nu[N] = 0;
     WIpm W = make_ipm(N, nx, nu.data(), nb, ng);
+    const WLayout& L = W.L;
     if (!ipm_check(W, N, nx, nu.data(), nb, idxb, ng)) return HPMPC_MI355X_EUNSUPPORTED;
     if (mode == WI_NEWTON) {
         for (int k = 0; k <= N; k++)
@@ -278,54 +262,42 @@ extern "C" int hk_wide_ipm_entry(int mode, int* kk, int k_max, double mu0, doubl
     fill_slots(W, N, idxb);
     const Stage S = carve(W, N, k_max);
     if (!g_dev.ensure(S.total)) return HPMPC_MI355X_EHIP;
-    char* H = g_dev.host;
-    stage_common(W, S, H, N, idxb, pBAbt, pQ, pDCt);
-    cvec_in(W, S, S.oD, H, N, d);
-    double* HU = reinterpret_cast<double*>(H + S.oU);
-    double* HP = reinterpret_cast<double*>(H + S.oP);
+    WideIpmArgs a;
+    stage(W, S, k_max, idxb, pBAbt, pQ, pDCt, d, a);
     if (mode == WI_NEWTON) {  // start iterate; lam0 / t0 as [lower (nb) | upper (nb)] (d_aux_ip_hard_lib4.c:153-213)
-        uvec_in(W, HU, N, ux0);
-        pvec_in(W, HP, N, pi0);
-        double* HL = reinterpret_cast<double*>(H + S.oLam);
-        double* HT = reinterpret_cast<double*>(H + S.oT);
+        uvec_in(L, S.ux.host(), ux0);
+        pvec_in(L, S.pi.host(), pi0);
         for (int k = 0; k <= N; k++) {
-            const WideStage& s = W.L.st[k];
+            const WideStage& s = L.st[k];
             for (int l = 0; l < nb[k]; l++) {
-                HL[s.oD + l] = lam0[k][l];
-                HL[s.oD + s.pnb + l] = lam0[k][nb[k] + l];
-                HT[s.oD + l] = t0[k][l];
-                HT[s.oD + s.pnb + l] = t0[k][nb[k] + l];
+                S.lam.host()[s.oD + l] = lam0[k][l];
+                S.lam.host()[s.oD + s.pnb + l] = lam0[k][nb[k] + l];
+                S.t.host()[s.oD + l] = t0[k][l];
+                S.t.host()[s.oD + s.pnb + l] = t0[k][nb[k] + l];
             }
         }
     } else if (warm_start) {
-        uvec_in(W, HU, N, ux);
+        uvec_in(L, S.ux.host(), ux);
     }
-    WideIpmArgs a;
-    fill_args(W, S, g_dev.dev, N, a);
     a.mode = mode;
-    a.k_max = k_max;
     a.warm_start = warm_start;
     a.compute_mult = compute_mult;
     a.mu0 = mu0;
     a.mu_tol = mu_tol;
     a.alpha_min = alpha_min;
     if (!run(W, S, a)) return HPMPC_MI355X_EHIP;
-    const int* iv = reinterpret_cast<const int*>(H + S.oCtl);
-    *kk = iv[0];
-    const double* Hs = reinterpret_cast<const double*>(H + S.oStat);
-    for (int i = 0; i < 5 * iv[0]; i++) stat[i] = Hs[i];
+    const IpmCtl& ctl = *S.ctl.host();
+    *kk = ctl.kk;
+    for (int i = 0; i < 5 * ctl.kk; i++) stat[i] = S.stat.host()[i];
     // d_ip2_mpc_hard_tv without constraints solves into its workspace only (d_ip2_hard.c:282-291)
-    const bool outputs = !(mode == WI_IPM_P1 && W.nbt == 0);
-    if (outputs) {
-        for (int k = 0; k <= N; k++) {
-            memcpy(ux[k], HU + W.L.st[k].oU, (W.L.st[k].nu + nx[k]) * sizeof(double));
-            if (k < N) memcpy(pi[k], HP + W.L.st[k].oP, nx[k + 1] * sizeof(double));
-        }
-        cvec_out(W, reinterpret_cast<const double*>(H + S.oLam), N, lam);
-        cvec_out(W, reinterpret_cast<const double*>(H + S.oT), N, t);
+    if (!(mode == WI_IPM_P1 && W.nbt == 0)) {
+        uvec_out(L, S.ux.host(), ux);
+        pvec_out(L, S.pi.host(), pi);
+        cvec_out(L, S.lam.host(), lam);
+        cvec_out(L, S.t.host(), t);
     }
-    memcpy(work, H + S.oIW, W.nIW * sizeof(double));
-    return iv[1];
+    memcpy(work, S.iw.host(), W.nIW * sizeof(double));
+    return ctl.ret;
 }
 
 // d_kkt_solve_new_rhs_res_mpc_hard_tv (p1 = 0: b / q / d) and d_kkt_solve_new_rhs_mpc_hard_tv (p1 = 1:
@@ -337,32 +309,26 @@ extern "C" void hk_wide_kkt_entry(int p1, int N, int* nx, int* nu_N, int* nb, in
     std::vector<int> nu(nu_N, nu_N + N + 1);
     nu[N] = 0;
     WIpm W = make_ipm(N, nx, nu.data(), nb, ng);
+    const WLayout& L = W.L;
     if (!ipm_check(W, N, nx, nu.data(), nb, idxb, ng)) return;
     fill_slots(W, N, idxb);
     const Stage S = carve(W, N, 1);
     if (!g_dev.ensure(S.total)) return;
-    char* H = g_dev.host;
-    stage_common(W, S, H, N, idxb, pBAbt, pQ, pDCt);
-    cvec_in(W, S, S.oD, H, N, d);
-    uvec_in(W, reinterpret_cast<double*>(H + S.ovq), N, q);
-    pvec_in(W, reinterpret_cast<double*>(H + S.ovb), N, b);
-    memcpy(H + S.oIW, work, W.nIW * sizeof(double));
     WideIpmArgs a;
-    fill_args(W, S, g_dev.dev, N, a);
+    stage(W, S, 0, idxb, pBAbt, pQ, pDCt, d, a);
+    uvec_in(L, S.vq.host(), q);
+    pvec_in(L, S.vb.host(), b);
+    memcpy(S.iw.host(), work, W.nIW * sizeof(double));
     a.mode = p1 ? WI_KKT_P1 : WI_KKT_RES;
     a.compute_mult = compute_mult;
-    a.vb = reinterpret_cast<const double*>(g_dev.dev + S.ovb);
-    a.vq = reinterpret_cast<const double*>(g_dev.dev + S.ovq);
+    a.vb = S.vb.dev();
+    a.vq = S.vq.dev();
     if (!run(W, S, a)) return;
-    const double* HU = reinterpret_cast<const double*>(H + S.oU);
-    const double* HP = reinterpret_cast<const double*>(H + S.oP);
-    for (int k = 0; k <= N; k++) {
-        memcpy(ux[k], HU + W.L.st[k].oU, (W.L.st[k].nu + nx[k]) * sizeof(double));
-        if (k < N && (compute_mult || !p1)) memcpy(pi[k], HP + W.L.st[k].oP, nx[k + 1] * sizeof(double));
-    }
-    cvec_out(W, reinterpret_cast<const double*>(H + S.oLam), N, lam);
-    cvec_out(W, reinterpret_cast<const double*>(H + S.oT), N, t);
-    if (p1) memcpy(work, H + S.oIW, W.nIW * sizeof(double));  // qx / Pb of the re-solve, as the reference leaves them
+    uvec_out(L, S.ux.host(), ux);
+    if (compute_mult || !p1) pvec_out(L, S.pi.host(), pi);
+    cvec_out(L, S.lam.host(), lam);
+    cvec_out(L, S.t.host(), t);
+    if (p1) memcpy(work, S.iw.host(), W.nIW * sizeof(double));  // qx / Pb of the re-solve, as the reference leaves them
 }
 
 // d_res_res_mpc_hard_tv (plain = 0: r_q, r_b, r_d, r_m, mu) and d_res_mpc_hard_tv (plain = 1: r_q, r_b, r_d, mu).
@@ -372,35 +338,30 @@ extern "C" void hk_wide_res_entry(int plain, int N, int* nx, int* nu, int* nb, i
                                   double** hrm, double* mu) {
     hk_set_error(0, nullptr);
     WIpm W = make_ipm(N, nx, nu, nb, ng);
+    const WLayout& L = W.L;
     if (!ipm_check(W, N, nx, nu, nb, idxb, ng)) return;
     fill_slots(W, N, idxb);
     const Stage S = carve(W, N, 1);
     if (!g_dev.ensure(S.total)) return;
-    char* H = g_dev.host;
-    stage_common(W, S, H, N, idxb, hpBAbt, hpQ, hpDCt);
-    cvec_in(W, S, S.oD, H, N, hd);
-    cvec_in(W, S, S.oLam, H, N, hlam);
-    cvec_in(W, S, S.oT, H, N, ht);
-    uvec_in(W, reinterpret_cast<double*>(H + S.oU), N, hux);
-    pvec_in(W, reinterpret_cast<double*>(H + S.oP), N, hpi);
-    uvec_in(W, reinterpret_cast<double*>(H + S.ovq), N, hq);
-    pvec_in(W, reinterpret_cast<double*>(H + S.ovb), N, hb);
-    reinterpret_cast<double*>(H + S.oCtl + 8)[0] = *mu;  // unchanged without constraints (d_res_ip_res_hard.c:309-313)
     WideIpmArgs a;
-    fill_args(W, S, g_dev.dev, N, a);
+    stage(W, S, 0, idxb, hpBAbt, hpQ, hpDCt, hd, a);
+    cvec_in(L, S.lam.host(), hlam);
+    cvec_in(L, S.t.host(), ht);
+    uvec_in(L, S.ux.host(), hux);
+    pvec_in(L, S.pi.host(), hpi);
+    uvec_in(L, S.vq.host(), hq);
+    pvec_in(L, S.vb.host(), hb);
+    S.ctl.host()->mu = *mu;  // unchanged without constraints (d_res_ip_res_hard.c:309-313)
     a.mode = plain ? WI_RES_PLAIN : WI_RES;
-    a.vb = reinterpret_cast<const double*>(g_dev.dev + S.ovb);
-    a.vq = reinterpret_cast<const double*>(g_dev.dev + S.ovq);
+    a.vb = S.vb.dev();
+    a.vq = S.vq.dev();
     if (!run(W, S, a)) return;
-    const double* IW = reinterpret_cast<const double*>(H + S.oIW);
-    for (int k = 0; k <= N; k++) {
-        const WideStage& s = W.L.st[k];
-        memcpy(hrq[k], IW + W.oRq + s.oU, (s.nu + s.nx) * sizeof(double));
-        if (k < N) memcpy(hrb[k], IW + W.oRb + s.oP, s.nx1 * sizeof(double));
-    }
-    cvec_out(W, IW + W.oC[4], N, hrd);
-    if (!plain) cvec_out(W, IW + W.oC[5], N, hrm);
-    *mu = reinterpret_cast<const double*>(H + S.oCtl + 8)[0];
+    const double* IW = S.iw.host();
+    uvec_out(L, IW + W.oRq, hrq);
+    pvec_out(L, IW + W.oRb, hrb);
+    cvec_out(L, IW + W.oC[4], hrd);
+    if (!plain) cvec_out(L, IW + W.oC[5], hrm);
+    *mu = S.ctl.host()->mu;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -410,20 +371,12 @@ extern "C" void hk_wide_res_entry(int plain, int N, int* nx, int* nu, int* nb, i
 struct hpmpc_mi355x_wide_plan {
     WIpm W;
     int N = 0;
-    WideStage* d_st = nullptr;
-    WideCSlot* d_cs = nullptr;
-    int* d_vbox = nullptr;
-    int* d_idxb = nullptr;
+    DevTable<WideStage> d_st;
+    DevTable<WideCSlot> d_cs;
+    DevTable<int> d_vbox, d_idxb;
 };
 
-extern "C" void hpmpc_mi355x_wide_plan_destroy(hpmpc_mi355x_wide_plan* q) {
-    if (!q) return;
-    if (q->d_st) (void)hipFree(q->d_st);
-    if (q->d_cs) (void)hipFree(q->d_cs);
-    if (q->d_vbox) (void)hipFree(q->d_vbox);
-    if (q->d_idxb) (void)hipFree(q->d_idxb);
-    delete q;
-}
+extern "C" void hpmpc_mi355x_wide_plan_destroy(hpmpc_mi355x_wide_plan* q) { delete q; }
 
 extern "C" hpmpc_mi355x_wide_plan* hpmpc_mi355x_wide_plan_create(int N, const int* nx, const int* nu_in, const int* nb,
                                                                  const int* const* idxb, const int* ng) {
@@ -441,20 +394,12 @@ extern "C" hpmpc_mi355x_wide_plan* hpmpc_mi355x_wide_plan_create(int N, const in
     fill_slots(q->W, N, ib);
     const WLayout& L = q->W.L;
     std::vector<int> hidx(L.nI, 0);
-    for (int k = 0; k <= N; k++)
-        for (int l = 0; l < nb[k]; l++) hidx[L.st[k].oI + l] = idxb[k][l];
-    const size_t ncs = q->W.cs.size() + 1;
-    bool ok = hip_ok(hipMalloc((void**)&q->d_st, sizeof(WideStage) * (N + 1)), "wide plan") &&
-              hip_ok(hipMalloc((void**)&q->d_cs, sizeof(WideCSlot) * ncs), "wide plan") &&
-              hip_ok(hipMalloc((void**)&q->d_vbox, sizeof(int) * L.nU), "wide plan") &&
-              hip_ok(hipMalloc((void**)&q->d_idxb, sizeof(int) * L.nI), "wide plan") &&
-              hip_ok(hipMemcpy(q->d_st, L.st.data(), sizeof(WideStage) * (N + 1), hipMemcpyHostToDevice), "plan") &&
-              (q->W.cs.empty() || hip_ok(hipMemcpy(q->d_cs, q->W.cs.data(), sizeof(WideCSlot) * q->W.cs.size(),
-                                                   hipMemcpyHostToDevice), "plan")) &&
-              hip_ok(hipMemcpy(q->d_vbox, q->W.vbox.data(), sizeof(int) * L.nU, hipMemcpyHostToDevice), "plan") &&
-              hip_ok(hipMemcpy(q->d_idxb, hidx.data(), sizeof(int) * L.nI, hipMemcpyHostToDevice), "plan");
-    if (!ok) {
-        hpmpc_mi355x_wide_plan_destroy(q);
+    idxb_in(L, hidx.data(), ib);
+    std::vector<WideCSlot> cs = q->W.cs;
+    cs.resize(cs.size() + 1);  // never an empty table
+    if (!q->d_st.upload(L.st, "wide plan") || !q->d_cs.upload(cs, "wide plan") ||
+        !q->d_vbox.upload(q->W.vbox, "wide plan") || !q->d_idxb.upload(hidx, "wide plan")) {
+        delete q;
         return nullptr;
     }
     return q;
@@ -491,82 +436,35 @@ extern "C" int hpmpc_mi355x_wide_ipm_batch(const hpmpc_mi355x_wide_plan* q, int 
     hk_set_error(0, nullptr);
     if (!q || nprob <= 0 || p0 < 0 || count < 0 || p0 + count > nprob || k_max < 0)
         return HPMPC_MI355X_EUNSUPPORTED;
-    const WIpm& W = q->W;
-    const WLayout& L = W.L;
     // every array the kernel dereferences unconditionally (DCt only when a stage has general constraints; stat is
     // nullable): a null one is a caller error, reported instead of faulting on the device
-    if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !work || !kk || !ret || (L.any_ng && !DCt)) {
+    if (!BAbt || !RSQrq || !d || !ux || !pi || !lam || !t || !work || !kk || !ret || (q->W.L.any_ng && !DCt)) {
         hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_wide_ipm_batch: null array");
         return HPMPC_MI355X_EUNSUPPORTED;
     }
     WideIpmArgs a;
-    memset(&a, 0, sizeof a);
-    a.w.N = q->N;
-    a.w.nprob = nprob;
-    a.w.p0 = p0;
-    a.w.st = q->d_st;
+    ipm_args(q->W, nprob, p0, k_max, a);
+    a.w.st = q->d_st.get();
     a.w.BAbt = BAbt;
-    a.w.sB = L.nB;
     a.w.RSQ = RSQrq;
-    a.w.sR = L.nR;
     a.w.DCt = DCt;
-    a.w.sG = L.nG;
-    a.w.idxb = q->d_idxb;
-    a.w.offW = L.offW;
-    a.w.offX = L.offX;
-    a.w.offV = L.offV;
-    a.w.offST = L.offST;
-    a.w.ldW = L.ldW;
-    a.w.ldX = L.ldX;
-    a.w.sU = L.nU;
-    a.w.sP = L.nP;
+    a.w.idxb = q->d_idxb.get();
     a.mode = WI_IPM_RES;
-    a.k_max = k_max;
     a.warm_start = warm_start;
     a.compute_mult = compute_mult;
     a.mu0 = mu0;
     a.mu_tol = mu_tol;
     a.alpha_min = alpha_min;
-    a.mu_scal = W.nbt ? 1.0 / (2.0 * (double)W.nbt) : 0.0;
-    a.nbt2 = 2.0 * (double)W.nbt;
-    a.ncs = (int)W.cs.size();
-    a.cs = q->d_cs;
-    a.vbox = q->d_vbox;
-    a.nU = (int)L.nU;
-    a.nP = (int)L.nP;
+    a.cs = q->d_cs.get();
+    a.vbox = q->d_vbox.get();
     a.d = d;
     a.ux = ux;
     a.pi = pi;
     a.lam = lam;
     a.t = t;
-    a.sC = L.nD;
     a.iw = work;
-    a.sI = W.nIW;
-    a.oF = W.oF;
-    a.oDux = W.oDux;
-    a.oDpi = W.oDpi;
-    a.oPb = W.oPb;
-    a.oRq = W.oRq;
-    a.oRb = W.oRb;
-    a.oUb = W.oUb;
-    a.oPib = W.oPib;
-    int* oc[10] = {&a.oDlam, &a.oDt, &a.oTinv, &a.oLamt, &a.oRd, &a.oRm, &a.oTb, &a.oLb, &a.oQx, &a.oqx};
-    for (int i = 0; i < 10; i++) *oc[i] = W.oC[i];
     a.stat = stat;
-    a.sS = 5LL * (k_max > 0 ? k_max : 1);
     a.kk = kk;
     a.ret = ret;
-    a.mu = nullptr;
-    a.offR = L.lds;
-    a.offKC = L.lds + 8;
-    if (count == 0) return 0;
-    const int e = hk_wide_ipm_launch(&a, count, ipm_lds(L), (hipStream_t)stream);
-    if (e) {
-        char msg[96];
-        snprintf(msg, sizeof msg, "hk_wide_ipm launch %s (%d)", e == -2 ? "refused: scratch / LDS beyond the limits" : "failed", e);
-        const int code = e == -2 ? HPMPC_MI355X_EUNSUPPORTED : HPMPC_MI355X_EHIP;
-        hk_set_error(code, msg);
-        return code;
-    }
-    return 0;
+    return count == 0 ? 0 : ipm_launch(q->W, a, count, (hipStream_t)stream);
 }

@@ -207,11 +207,18 @@ TOL_PCOND_SV = 1e-11  # condensed pipeline vs the reference's direct Riccati (or
 
 
 def check_pcond(case, got):
-    """Condensed data of d_part_cond (lower triangle of RSQrq2: the only part any consumer reads) and the
-    expanded solution."""
+    """Condensed data of d_part_cond (check_pcond_data) and the expanded solution."""
+    check_pcond_data(case, got["cqp"])
+    for key in ("ux", "pi", "lam", "t"):
+        e = max_err(case, key, got[key], case.out[key])
+        assert e <= TOL_RIC, f"{case.name}: {key} err {e:.3e}"
+
+
+def check_pcond_data(case, c):
+    """Condensed data of d_part_cond (lower triangle of RSQrq2: the only part any consumer reads)."""
     from hpmpc_amd.ocp import unpack_lib4
 
-    out, c = case.out, got["cqp"]
+    out = case.out
     for f in ("nx2", "nu2", "nb2", "ng2"):
         np.testing.assert_array_equal(getattr(c, f[:2]), out[f], err_msg=case.name + f)
     N2 = c.N
@@ -232,9 +239,6 @@ def check_pcond(case, got):
         np.testing.assert_allclose(c.d[k][idx], out["d2"][k][idx], rtol=TOL_RIC, atol=TOL_RIC,
                                    err_msg=f"{case.name} d2[{k}]")
         np.testing.assert_array_equal(c.idxb[k], out["idxb2"][k].astype(np.int32), err_msg=f"{case.name} idxb2")
-    for key in ("ux", "pi", "lam", "t"):
-        e = max_err(case, key, got[key], out[key])
-        assert e <= TOL_RIC, f"{case.name}: {key} err {e:.3e}"
 
 
 def _valid_len(case, key, k):

@@ -409,3 +409,41 @@ def test_pcond_deferred_cross_terms_bitwise(shape):
             os.environ.pop("HPMPC_MI355X_PCOND_DM", None)
     for name, a, b in zip(("BAbt2", "RSQrq2", "DCt2", "d2"), *out):
         assert torch.equal(a, b), name
+
+
+def test_pcond_long_block_every_state_boxed(product, oracle):
+    """One 24-stage block with every input and state boxed: d_cond_DCtd's integer bookkeeping (6 T + 2 ng2 = 512 ints
+    at the start of LDS) reaches past the BAbt tile (424 ints), which the deferred cross terms would overwrite while they
+    still read it, so the plan takes the reference's order for this shape (tests/host/wide_plan_check.cpp pins that).
+    HPMPC_MI355X_PCOND_DM therefore changes nothing, bitwise, and problem 0 through d_part_cond matches the oracle."""
+    import torch
+
+    from hpmpc_amd.golden import Case
+    from hpmpc_amd.pcond import PcondSolver
+    from helpers import check_pcond_data, stack_qps
+
+    N, N2 = 24, 1
+    nx, nu = [0] + [8] * N, [1] * (N + 1)
+    nb = [nu[k] + nx[k] for k in range(N)] + [nx[N]]
+    qps = [random_qp(N, nx, nu, nb=nb, seed=900 + i, coupling=0.1) for i in range(4)]
+    c, _ = oracle.part_cond(qps[0].copy(), N2)
+    like = Case.__new__(Case)
+    like.name, like.qp = "pcond_long_block", qps[0]
+    like.out = dict(BAbt2=c.BAbt, RSQrq2=c.RSQrq[:N2], DCt2=c.DCt[:N2] if c.DCt else [], d2=c.d[:N2],
+                    idxb2=[i.astype(np.float64) for i in c.idxb[:N2]], nx2=c.nx, nu2=c.nu, nb2=c.nb, ng2=c.ng)
+    assert int(c.ng[0]) == 23 * 8
+    gc, _ = product.part_cond(qps[0].copy(), N2)
+    check_pcond_data(like, gc)
+    qp = stack_qps(qps)
+    out = []
+    for dm in ("1", "0"):
+        os.environ["HPMPC_MI355X_PCOND_DM"] = dm
+        try:
+            s = PcondSolver(qp, N2)
+            s.condense()
+            torch.cuda.synchronize()
+            out.append([t.clone() for t in (s.BAbt2, s.RSQrq2, s.DCt2, s.d2)])
+        finally:
+            os.environ.pop("HPMPC_MI355X_PCOND_DM", None)
+    for name, a, b in zip(("BAbt2", "RSQrq2", "DCt2", "d2"), *out):
+        assert torch.equal(a, b), name
