@@ -156,6 +156,25 @@ def kkt_tangent_call(torch, plan, layout, N, nprob, p0, count, ndir, BAbt, RSQrq
                      N, nprob, p0, count, ndir, BAbt, RSQrq, DCt, (db, dq, dd), out, ws, compute_mult, stream)
 
 
+def kkt_adjoint_call(torch, plan, layout, N, nprob, p0, count, nadj, BAbt, RSQrq, DCt, gux, gpi, glam, gt, out, ws,
+                     want_b, stream) -> int:
+    """hpmpc_mi355x_kkt_adjoint_batch on torch tensors, after checking the shapes of the per-set cotangents: gux, gpi
+    (nprob, nadj, N+1, 16), glam, gt (nprob, nadj, N+1, 32), each or all None (zero); ``out`` from kkt_buffers(nadj),
+    whose pi / ux / lam receive bbar / qbar / dbar (bbar only with ``want_b``; its t is not touched).  Returns the
+    library's code."""
+    for name, x, w in (("gux", gux, 16), ("gpi", gpi, 16), ("glam", glam, 32), ("gt", gt, 32)):
+        if x is not None and (tuple(x.shape) != (nprob, nadj, N + 1, w) or x.dtype != torch.float64 or
+                              not x.is_contiguous()):
+            raise ValueError(f"{name}: contiguous float64 tensor of shape {(nprob, nadj, N + 1, w)} expected")
+    for name, w in (("ux", 16), ("pi", 16), ("lam", 32)):
+        if tuple(out[name].shape) != (nprob, nadj, N + 1, w):
+            raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={nadj}) expected")
+    ptr = lambda x: None if x is None else x.data_ptr()
+    return lib().hpmpc_mi355x_kkt_adjoint_batch(
+        plan, layout, nprob, p0, count, nadj, ptr(BAbt), ptr(RSQrq), ptr(DCt), ptr(gux), ptr(gpi), ptr(glam), ptr(gt),
+        ptr(out["pi"]) if want_b else None, ptr(out["ux"]), ptr(out["lam"]), ptr(ws), ptr(out["scratch"]), stream)
+
+
 class BatchSolver:
     """Device-resident batch of OCP QPs + the batched HPMPC entry points.
 
@@ -287,6 +306,21 @@ class BatchSolver:
                                self.BAbt, self.RSQrq, None, db, dq, dd, out, self.ws, compute_mult, self._stream()),
               "hpmpc_mi355x_kkt_tangent_batch")
         return out["ux"], out["pi"], out["lam"], out["t"]
+
+    def kkt_adjoint(self, gux, gpi, glam, gt, nadj=1, p0=0, count=None, want_b=True, out=None):
+        """Batched KKT adjoint solve (hpmpc_mi355x_kkt_adjoint_batch): the transpose of kkt_tangent, ``nadj`` cotangent
+        sets per problem in one launch, on the factor ipm() / ipm_solo() left.  gux, gpi: (nprob, nadj, N+1, 16), glam,
+        gt: (nprob, nadj, N+1, 32), the cotangents of kkt_new_rhs's ux, pi, lam, t, or None for zero.  Returns (bbar,
+        qbar, dbar), the gradients with respect to b, q and d, with a leading (nprob, nadj) shape: the pi, ux and lam
+        tensors of ``out`` (default: those of kkt_buffers(nadj), which the next kkt_new_rhs / kkt_tangent /
+        kkt_adjoint call of that set count overwrites).  want_b=False skips the multiplier half of the solve and
+        returns bbar as None.  ws and the problem data are not written.  Asynchronous on torch's current stream."""
+        count = self.nprob - p0 if count is None else count
+        out = self.kkt_buffers(nadj) if out is None else out
+        check(kkt_adjoint_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, nadj,
+                               self.BAbt, self.RSQrq, None, gux, gpi, glam, gt, out, self.ws, want_b, self._stream()),
+              "hpmpc_mi355x_kkt_adjoint_batch")
+        return (out["pi"] if want_b else None), out["ux"], out["lam"]
 
     def ipm_pass(self, pss, *, mu0=2.0, mu_tol=1e-12, alpha_min=1e-8, warm_start=0, compute_mult=1, p0=0,
                  count=None):

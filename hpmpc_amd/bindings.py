@@ -63,6 +63,8 @@ _SIG = dict(
     ocp_unpack_sets="i:piiiippppppppppp",
     kkt_tangent_batch="i:ppiiiippppppppppppip",
     ocp_tangent_batch="i:ppiiiippppppppppip",
+    kkt_adjoint_batch="i:ppiiiippppppppppppp",
+    ocp_adjoint_batch="i:piiiipppppppppppppppppp",
 )
 # {function name: (restype, argtypes)}
 SIGNATURES = {"hpmpc_mi355x_" + n: (_CTYPE[s[0]], [_CTYPE[c] for c in s[2:]]) for n, s in _SIG.items()}

@@ -25,7 +25,8 @@ struct KktArgs {
     long long sS;
 };
 
-// The ten work vectors of the set whose scratch block starts at S (hk_kkt_tan; hk_kkt_rhs writes the same lines out).
+// The ten work vectors of the set whose scratch block starts at S (hk_kkt_tan, hk_kkt_adj; hk_kkt_rhs writes the same
+// lines out).
 struct KktSet {
     double *res_q, *res_b, *qx, *dux, *dpi, *Pb, *res_d, *res_m, *dt, *dlam;
 };

@@ -1,5 +1,5 @@
-// hk_kkt_launch.h -- the launcher of the one-wavefront-per-set kernels hk_kkt_rhs (hk_kkt.hip) and hk_kkt_tan
-// (hk_tan.hip): grid = count problems x `sets` sets per problem, the LDS stage tables, the launch guard.
+// hk_kkt_launch.h -- the launcher of the one-wavefront-per-set kernels hk_kkt_rhs (hk_kkt.hip), hk_kkt_tan
+// (hk_tan.hip) and hk_kkt_adj (hk_adj.hip): grid = count problems x `sets` sets per problem, the LDS stage tables, the launch guard.
 #pragma once
 #include "hk_ipm_body.h"
 #include "hk_launch_guard.h"

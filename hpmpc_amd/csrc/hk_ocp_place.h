@@ -1,6 +1,7 @@
 // hk_ocp_place.h -- where the OCP front end's dense vectors sit in the solver's padded stage vectors, and back: one
 // definition of each placement for hk_ocp_pack, hk_ocp_pack_vectors, hk_ocp_unpack (hk_ocp.hip) and the dense prologue
-// and epilogue of hk_kkt_tan (hk_tan.hip).  Device code only; lane l of a wavefront owns one element.
+// and epilogue of hk_kkt_tan (hk_tan.hip), and the transposes of both for those of hk_kkt_adj (hk_adj.hip).  Device code
+// only; lane l of a wavefront owns one element.
 //
 // In: stage k's seed row, 64 doubles -- lanes 0..15 b_k (state order), 16..31 [r_k | q_k] (variable order), 32..63 d_k =
 // [lb pnb | ub pnb | lg png | ug png]; and the warm start ux_k = [u0_k | x0_k | 0 ..].
@@ -84,6 +85,76 @@ __device__ __forceinline__ void ocp_unpack_store(const OcpStage& s, const OcpOut
         const int e = 2 * s.dn[OCP_lb] + 2 * s.dn[OCP_lg] + l;
         o.lam[e] = lam;
         if (o.t) o.t[e] = t;
+    }
+}
+
+// ---- the adjoint's placements (hk_kkt_adj, hk_adj.hip): the transposes of the two above ----
+
+// The dense cotangents of one set, already offset to it (null: zeros): u, x, pi shaped like r, q, b, lam / t compact.
+struct OcpCots {
+    const double *u, *x, *pi, *lam, *t;
+};
+
+// Padded slot c of a compact constraint array `a` (lam or t), the transpose of ocp_unpack_store's gather through
+// compact_src: zero bits for padding, a slot out of range and a null array.
+__device__ __forceinline__ long long ocp_compact_bits(const OcpStage& s, const double* a, int c) {
+    const int cu = c - s.pnb, cg = c - 2 * s.pnb, ch = c - 2 * s.pnb - s.png;
+    const int base = 2 * s.dn[OCP_lb] + 2 * s.dn[OCP_lg];
+    const double w[4] = {hk::gld(a, base + c, a && c >= 0 && c < s.nb),
+                         hk::gld(a, base + s.nb + cu, a && cu >= 0 && cu < s.nb),
+                         hk::gld(a, base + 2 * s.nb + cg, a && cg >= 0 && cg < s.ng),
+                         hk::gld(a, base + 2 * s.nb + s.ng + ch, a && ch >= 0 && ch < s.ng)};
+    long long bits = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) bits |= __double_as_longlong(w[i]);
+    return bits;
+}
+// Lane l's element of stage k's cotangent row, the transpose of ocp_unpack_store without the equality-box fix: lanes
+// 0..15 gpi_k (state order), 16..31 gux_k = [gu_k | gx_k] (variable order), 32..63 the padded glam_k.  The padded gt_k
+// is ocp_compact_bits(s, g.t, l - 32).  OR-ed masked loads, as in ocp_seed_bits.
+__device__ __forceinline__ long long ocp_cot_bits(const OcpStage& s, const OcpCots& g, int l) {
+    const int e = l & 15;
+    const bool isp = l < 16, isv = l >= 16 && l < 32;
+    const double w[3] = {hk::gld(g.pi, s.dn[OCP_b] + e, isp && g.pi && e < s.nx1),
+                         hk::gld(g.u, s.dn[OCP_r] + e, isv && g.u && e < s.nu),
+                         hk::gld(g.x, s.dn[OCP_q] + (e - s.nu), isv && g.x && e >= s.nu && e < s.nu + s.nx)};
+    long long bits = ocp_compact_bits(s, g.lam, l - 32);
+#pragma unroll
+    for (int i = 0; i < 3; i++) bits |= __double_as_longlong(w[i]);
+    return bits;
+}
+
+// The dense gradients of one set, already offset to it (null: not wanted), shaped like the data arrays.
+struct OcpGrads {
+    double *b, *q, *r, *lb, *ub, *lg, *ug;
+};
+
+// Whether lane l's slot of the 64-double stage row [state order (16) | variable order (16) | d_k (32)] carries an
+// element (not padding).
+__device__ __forceinline__ bool ocp_row_live(const OcpStage& s, int l) {
+    const int e = l & 15, c = l - 32;
+    const int cu = c - s.pnb, cg = c - 2 * s.pnb, ch = c - 2 * s.pnb - s.png;
+    if (l < 16) return e < s.nx1;
+    if (l < 32) return e < s.nu + s.nx;
+    return c < s.nb || (cu >= 0 && cu < s.nb) || (cg >= 0 && cg < s.ng) || (ch >= 0 && ch < s.ng);
+}
+
+// Lane l's store of stage k's gradient row [bbar_k (16) | qbar_k (16) | dbar_k (32)]: the exact transpose of
+// ocp_seed_bits, which copies each dense element to one slot with unit weight -- so each slot goes back to that
+// element, unscaled, and padding slots go nowhere.
+__device__ __forceinline__ void ocp_grad_store(const OcpStage& s, const OcpGrads& o, int l, double v) {
+    const int e = l & 15, c = l - 32;
+    const int cu = c - s.pnb, cg = c - 2 * s.pnb, ch = c - 2 * s.pnb - s.png;
+    if (l < 16) {
+        if (o.b && e < s.nx1) o.b[s.dn[OCP_b] + e] = v;
+    } else if (l < 32) {
+        if (o.r && e < s.nu) o.r[s.dn[OCP_r] + e] = v;
+        if (o.q && e >= s.nu && e < s.nu + s.nx) o.q[s.dn[OCP_q] + (e - s.nu)] = v;
+    } else {
+        if (o.lb && c < s.nb) o.lb[s.dn[OCP_lb] + c] = v;
+        if (o.ub && cu >= 0 && cu < s.nb) o.ub[s.dn[OCP_ub] + cu] = v;
+        if (o.lg && cg >= 0 && cg < s.ng) o.lg[s.dn[OCP_lg] + cg] = v;
+        if (o.ug && ch >= 0 && ch < s.ng) o.ug[s.dn[OCP_ug] + ch] = v;
     }
 }
 

@@ -1,5 +1,5 @@
 // hk_ocp_plan.h -- the OCP plan of the batched OCP front end, shared by hpmpc_capi_ocp.cpp (which creates it) and
-// hpmpc_capi_kkt.cpp (the dense tangent call): a tile plan, whose packed default layout the lib4
+// hpmpc_capi_kkt.cpp (the dense tangent and adjoint calls): a tile plan, whose packed default layout the lib4
 // and vector arrays follow, and the device tables of stage sizes, dense offsets (OcpStage, hk_ocp_args.h) and box
 // indices.
 #pragma once

@@ -3,10 +3,12 @@
 // (mpc_solvers/d_ip2_res_hard.c:1922-2299) on device-resident batches, nrhs right-hand-side sets per problem
 // (hk_kkt_rhs, hk_kkt.hip); and its linear part, the KKT tangent solve hpmpc_mi355x_kkt_tangent_batch (padded
 // directions and results, the re-solve's layouts) and hpmpc_mi355x_ocp_tangent_batch (dense directions and results on
-// an OCP plan), ndir direction sets per problem (hk_kkt_tan, hk_tan.hip).  The workspaces an IPM left
-// (hpmpc_mi355x_ipm_batch, _ipm_solo, _ocp_ipm_batch) are read only; each set's work vectors live in the caller's
-// scratch (kkt_scratch_doubles, hk_kkt_args.h).  The core calls carry a DCt array, so they take tile plans with
-// general constraints (batch_args with DCT_ARRAY).
+// an OCP plan), ndir direction sets per problem (hk_kkt_tan, hk_tan.hip); and that tangent's transpose, the KKT adjoint
+// solve hpmpc_mi355x_kkt_adjoint_batch / hpmpc_mi355x_ocp_adjoint_batch, nadj cotangent sets per problem (hk_kkt_adj,
+// hk_adj.hip).  The workspaces an IPM left (hpmpc_mi355x_ipm_batch, _ipm_solo, _ocp_ipm_batch) are read only; each
+// set's work vectors live in the caller's scratch (kkt_scratch_doubles, hk_kkt_args.h).  The core calls carry a DCt
+// array, so they take tile plans with general constraints (batch_args with DCT_ARRAY).
+#include "hk_adj_args.h"
 #include "hk_ocp_plan.h"
 #include "hk_tan_args.h"
 
@@ -139,5 +141,66 @@ extern "C" int hpmpc_mi355x_ocp_tangent_batch(const hpmpc_mi355x_ocp_plan* O, co
     x.out = out;
     if (const int e = hk_kkt_tan_launch(&a, &x, count, (hipStream_t)stream))
         return launch_error(e, "hk_kkt_tan launch failed");
+    return g_err = 0;
+}
+
+// A null cotangent is zero; a null bbar skips the multiplier half of the solve.
+extern "C" int hpmpc_mi355x_kkt_adjoint_batch(const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob,
+                                              int p0, int count, int nadj, const double* BAbt, const double* RSQrq,
+                                              const double* DCt, const double* gux, const double* gpi,
+                                              const double* glam, const double* gt, double* bbar, double* qbar,
+                                              double* dbar, const double* ws, double* scratch, void* stream) {
+    KArgs a;
+    AdjArgs x;
+    memset(&x, 0, sizeof x);
+    if (!sets_args(a, x.k, plan, lay, nprob, p0, count, nadj, BAbt, RSQrq, DCt, ws, scratch, qbar && dbar, bbar ? 1 : 0,
+                   "hpmpc_mi355x_kkt_adjoint_batch", "hpmpc_mi355x adjoint call: nadj"))
+        return g_err;
+    set_arrays(a, gpi, gux, nullptr, qbar, bbar, dbar, nullptr);  // hk_adj_args.h: which KArgs field carries what
+    x.glam = glam;
+    x.gt = gt;
+    if (const int e = hk_kkt_adj_launch(&a, &x, count, (hipStream_t)stream))
+        return launch_error(e, "hk_kkt_adj launch failed");
+    return g_err = 0;
+}
+
+extern "C" int hpmpc_mi355x_ocp_adjoint_batch(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nadj,
+                                              const double* BAbt, const double* RSQrq, const double* DCt,
+                                              const double* gu, const double* gx, const double* gpi,
+                                              const double* glam, const double* gt, double* gb, double* gq, double* gr,
+                                              double* glb, double* gub, double* glg, double* gug, const double* ws,
+                                              double* scratch, void* stream) {
+    if (!O) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_adjoint_batch: plan");
+        return g_err;
+    }
+    KArgs a;
+    AdjArgs x;
+    memset(&x, 0, sizeof x);
+    const bool any = gb || gq || gr || glb || gub || glg || gug;
+    if (!sets_args(a, x.k, O->tile.get(), nullptr, nprob, p0, count, nadj, BAbt, RSQrq, DCt, ws, scratch, any,
+                   gb && O->dense[OCP_b] > 0, "hpmpc_mi355x_ocp_adjoint_batch", "hpmpc_mi355x adjoint call: nadj"))
+        return g_err;
+    const double* cot[5] = {gu, gx, gpi, glam, gt};
+    const long long scot[5] = {O->su, O->sx, O->sp, O->sl, O->sl};
+    for (int i = 0; i < 5; i++) {
+        if (scot[i] > 0) {  // a cotangent the plan has no element of is never read
+            x.cot[i].p = cot[i];
+            x.cot[i].s = scot[i];
+        }
+    }
+    const struct {
+        int i;
+        double* p;
+    } grads[] = {{OCP_b, gb}, {OCP_q, gq}, {OCP_r, gr}, {OCP_lb, glb}, {OCP_ub, gub}, {OCP_lg, glg}, {OCP_ug, gug}};
+    for (const auto& g : grads) {
+        if (O->dense[g.i] > 0) {
+            x.grad.p[g.i] = g.p;
+            x.grad.s[g.i] = O->dense[g.i];
+        }
+    }
+    x.ost = O->d_st.get();
+    if (const int e = hk_kkt_adj_launch(&a, &x, count, (hipStream_t)stream))
+        return launch_error(e, "hk_kkt_adj launch failed");
     return g_err = 0;
 }

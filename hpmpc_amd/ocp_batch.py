@@ -154,6 +154,45 @@ def tangent_set_arrays(problem_deltas):
     return kkt_set_arrays(full)
 
 
+def adjoint_set_arrays(problem_cotangents):
+    """The cotangent twin of tangent_set_arrays: dense interface-form COTANGENTS (dicts with N, nx, nu, nb, ng and any
+    of u, x, pi, lam, t as per-stage lists shaped like the outputs -- lam / t compact [lb nb | ub nb | lg ng | ug ng];
+    a missing key is zero) -> gux (n, N+1, 16) in variable order [gu_k | gx_k], gpi (n, N+1, 16) in state order, glam,
+    gt (n, N+1, 32) as [lb pnb | ub pnb | lg png | ug png], padding zero -- the arrays of
+    hpmpc_mi355x_kkt_adjoint_batch.  The placement is the transpose of the dense outputs' (the gather a padded iterate
+    goes through on its way to u, x, pi, lam, t, without the equality-box fix): sum(dense(it) * g) == sum(it *
+    adjoint_set_arrays(g)) for every padded iterate it."""
+    N, nx, nu, nb, ng = _sizes_of(problem_cotangents[0])
+    n = len(problem_cotangents)
+    gux, gpi = np.zeros((n, N + 1, 16)), np.zeros((n, N + 1, 16))
+    glam, gt = np.zeros((n, N + 1, 32)), np.zeros((n, N + 1, 32))
+    for p, G in enumerate(problem_cotangents):
+        if _sizes_of(G) != (N, nx, nu, nb, ng):
+            raise ValueError("the problems of a batch share their stage sizes")
+        blk = lambda key, k: None if G.get(key) is None or k >= len(G[key]) else np.asarray(G[key][k], dtype=np.float64)
+        for k in range(N + 1):
+            nuk = int(nu[k]) if k < N else 0
+            nxk, nbk, ngk = int(nx[k]), int(nb[k]), int(ng[k])
+            pnb, png = (nbk + 3) // 4 * 4, (ngk + 3) // 4 * 4
+            if k < N and blk("u", k) is not None:
+                gux[p, k, :nuk] = blk("u", k)
+            if blk("x", k) is not None:
+                gux[p, k, nuk:nuk + nxk] = blk("x", k)
+            if k < N and blk("pi", k) is not None:
+                gpi[p, k, :int(nx[k + 1])] = blk("pi", k)
+            for key, arr in (("lam", glam), ("t", gt)):
+                v = blk(key, k)
+                if v is None:
+                    continue
+                if v.shape != (2 * nbk + 2 * ngk,):
+                    raise ValueError(f"{key}[{k}] has shape {v.shape}, expected {(2 * nbk + 2 * ngk,)}")
+                arr[p, k, :nbk] = v[:nbk]
+                arr[p, k, pnb:pnb + nbk] = v[nbk:2 * nbk]
+                arr[p, k, 2 * pnb:2 * pnb + ngk] = v[2 * nbk:2 * nbk + ngk]
+                arr[p, k, 2 * pnb + png:2 * pnb + png + ngk] = v[2 * nbk + ngk:]
+    return gux, gpi, glam, gt
+
+
 def x0_directions(A0, S0=None):
     """The nx0 parameter directions of an initial state x_0 that is folded into stage 0 (nx[0] = 0, b_0 = A_0 x_0 + b,
     r_0 = r + S_0 x_0): direction i is db_0 = A_0[:, i] and, with S0, dr_0 = S_0[:, i].  A0: (..., nx[1], nx0), S0:
@@ -187,7 +226,7 @@ def ocp_plan_create(N, nx, nu, nb, idxb, ng, order="C"):
 class OcpBatchSolver:
     """``nprob`` OCPs with the given stage sizes: owns the lib4 arrays, the iterate, the workspaces and the outputs
     (torch tensors on ``device``).  pack() -> solve() -> finish(), then any number of resolve() -> finish() or
-    kkt_sets() / tangent() on the factor solve() left, all asynchronous on torch's current stream.
+    kkt_sets() / tangent() / adjoint() on the factor solve() left, all asynchronous on torch's current stream.
     There is no CPU fallback: without a GPU or the built library the constructor raises."""
 
     def __init__(self, N, nx, nu, nb, idxb, ng, nprob, order="C", device="cuda", k_max=50):
@@ -431,6 +470,97 @@ class OcpBatchSolver:
             dirs[key] = full
         du = self.tangent(dirs, nx0, p0=p0, count=count)["u"]
         return du[:, :, :self.nu[0]].transpose(1, 2)
+
+    def grad_buffers(self, nadj: int = 1) -> dict:
+        """The dense per-set gradient tensors b, q, r, lb, ub, lg, ug of shape (nprob, nadj, max(size, 1)) that
+        adjoint(nadj=nadj) writes (allocated on first use, then reused and overwritten)."""
+        if nadj < 1:
+            raise ValueError("at least one set per problem expected")
+        bufs = self.__dict__.setdefault("_grads", {})
+        if nadj not in bufs:
+            new = lambda n: self.torch.zeros((self.nprob, nadj, max(n, 1)), dtype=self.torch.float64, device=self.dev)
+            bufs[nadj] = {key: new(self.sizes[key]) for key in VEC_KEYS}
+        return bufs[nadj]
+
+    def adjoint(self, cot, nadj, p0=0, count=None, want=VEC_KEYS):
+        """Reverse sensitivities of the re-solved plan (hpmpc_mi355x_ocp_adjoint_batch), the transpose of tangent():
+        for ``nadj`` cotangent sets per problem -- each the gradient of a scalar loss with respect to what resolve()
+        computes -- that loss's gradient with respect to b, q, r and the bounds, one Riccati solve per set on the
+        factor of solve().  ``cot``: {key: contiguous float64 device tensor (nprob, nadj, size)} for any of u, x, pi,
+        lam, t (the sizes of the outputs; lam / t compact); a missing (or None) key is zero.  Returns {key: (nprob,
+        nadj, sizes[key])} over ``want`` (default all of b, q, r, lb, ub, lg, ug) -- tensors of grad_buffers(nadj);
+        a key left out of ``want`` is not written, and without "b" the multiplier half of the solve is skipped.
+        Neither ws nor the solver's data or iterate is written."""
+        torch = self.torch
+        p0, count = self._range(p0, count)
+        if not want or any(key not in VEC_KEYS for key in want):
+            raise ValueError(f"want: a non-empty subset of {VEC_KEYS} expected")
+        s = self.sizes
+        size = dict(u=s["u"], x=s["x"], pi=s["pi_out"], lam=s["lam_out"], t=s["lam_out"])
+        ptrs = []
+        for key in OUT_KEYS:
+            x = cot.get(key)
+            if x is not None and (x.dtype != torch.float64 or x.device.type != self.dev.type or not x.is_contiguous()
+                                  or tuple(x.shape) != (self.nprob, nadj, size[key])):
+                raise ValueError(f"cotangent {key}: contiguous float64 tensor ({self.nprob}, {nadj}, {size[key]}) on "
+                                 f"{self.dev} expected")
+            ptrs.append(None if x is None else x.data_ptr())
+        if any(key not in OUT_KEYS for key in cot):
+            raise ValueError(f"cotangents are keyed by {OUT_KEYS}")
+        g = self.grad_buffers(nadj)
+        check(lib().hpmpc_mi355x_ocp_adjoint_batch(
+            self.plan, self.nprob, p0, count, nadj, *self._lib4(), *ptrs,
+            *(g[key].data_ptr() if key in want else None for key in VEC_KEYS), self.ws.data_ptr(),
+            self.kkt_buffers(nadj)["scratch"].data_ptr(), self._stream()), "hpmpc_mi355x_ocp_adjoint_batch")
+        return {key: g[key][..., :s[key]] for key in VEC_KEYS if key in want}
+
+    def adjoint_sets(self, gux, gpi, glam, gt, nadj=1, p0=0, count=None, want_b=True):
+        """The padded core of adjoint() (hpmpc_mi355x_kkt_adjoint_batch with the tile plan on the packed arrays): gux,
+        gpi (nprob, nadj, N+1, 16), glam, gt (nprob, nadj, N+1, 32) device tensors (adjoint_set_arrays builds them) or
+        None for zero.  Returns (bbar, qbar, dbar) with a leading (nprob, nadj) shape in the padded layouts of b, q and
+        d -- the pi, ux, lam tensors of kkt_buffers(nadj), which kkt_sets / tangent_sets of that set count also write.
+        want_b=False: the multiplier half is skipped, bbar is None and the pi buffer is not written."""
+        from .batch import kkt_adjoint_call
+
+        p0, count = self._range(p0, count)
+        out = self.kkt_buffers(nadj)
+        check(kkt_adjoint_call(self.torch, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), None, self.N, self.nprob, p0,
+                               count, nadj, *self._lib4(ptr=False), gux, gpi, glam, gt, out, self.ws, want_b,
+                               self._stream()), "hpmpc_mi355x_kkt_adjoint_batch")
+        return (out["pi"] if want_b else None), out["ux"], out["lam"]
+
+    def x0_gradient(self, A0, S0, grads):
+        """The chain rule of x0_directions: the gradient with respect to an x_0 folded into stage 0 (b_0 = A_0 x_0 + b,
+        r_0 = r + S_0 x_0), A_0' gb_0 + S_0' gr_0, from the ``grads`` adjoint() returned ("b", and "r" with S0).
+        A0: (nprob, nx[1], nx0) or (nx[1], nx0), S0 likewise (nu[0], nx0) or None.  Returns (nprob, nadj, nx0)."""
+        torch = self.torch
+        if self.nx[0] != 0:
+            raise ValueError("x0_gradient: x_0 is folded into stage 0 (nx[0] = 0)")
+        dev = lambda M: torch.as_tensor(M, dtype=torch.float64).to(self.dev)
+        # a 2-D block is shared by every problem
+        mul = lambda M, g: torch.einsum("ji,prj->pri" if dev(M).dim() == 2 else "pji,prj->pri", dev(M), g)
+        A0 = dev(A0)
+        if A0.shape[-2] != self.nx[1]:
+            raise ValueError(f"x0_gradient: A0 has {self.nx[1]} rows")
+        out = mul(A0, grads["b"][:, :, :self.nx[1]])  # stage 0's block starts every problem's array
+        if S0 is not None:
+            if tuple(dev(S0).shape[-2:]) != (self.nu[0], A0.shape[-1]):
+                raise ValueError("x0_gradient: A0 and S0 have one column per component of x_0")
+            out = out + mul(S0, grads["r"][:, :, :self.nu[0]])
+        return out
+
+    def feedback_gain_adjoint(self, A0, S0=None, p0=0, count=None):
+        """feedback_gain by reverse mode: d u_0 / d x_0, (nprob, nu[0], nx0), from nu[0] adjoint sets instead of nx0
+        tangent sets -- set i has the cotangent e_i on u_0, and row i of the gain is its x0_gradient."""
+        torch = self.torch
+        if self.nx[0] != 0:
+            raise ValueError("feedback_gain_adjoint: x_0 is folded into stage 0 (nx[0] = 0)")
+        nu0 = self.nu[0]
+        gu = torch.zeros((self.nprob, nu0, self.sizes["u"]), dtype=torch.float64, device=self.dev)
+        idx = torch.arange(nu0, device=self.dev)
+        gu[:, idx, idx] = 1.0  # stage 0's block starts every problem's u
+        grads = self.adjoint({"u": gu}, nu0, p0=p0, count=count, want=("b",) if S0 is None else ("b", "r"))
+        return self.x0_gradient(A0, S0, grads)
 
     def finish(self, p0=0, count=None) -> dict:
         """The wrappers' outputs as device tensors (nprob, size): u, x (equality-box fix applied), pi, compact lam

@@ -632,8 +632,8 @@ int hpmpc_mi355x_ocp_unpack_sets(const hpmpc_mi355x_ocp_plan *plan, int nprob, i
  * compute_mult = 0: dpi is returned as zeros.  Asynchronous on `stream`, synchronises with nothing; only the sets of
  * problems [p0, p0+count) are read or written; count = 0 returns 0.  ndir < 1, a bad range, a null required pointer,
  * a null DCt with ng > 0 or a refused launch return HPMPC_MI355X_EUNSUPPORTED and write nothing.
- * Out of scope, refused or absent rather than half-built: reverse mode (adjoint solves), directions in the matrices
- * (A, B, Q, S, R, C, D), and per-set residual norms. */
+ * Reverse mode is the adjoint solve below.  Out of scope, refused or absent rather than half-built: directions in the
+ * matrices (A, B, Q, S, R, C, D), and per-set residual norms. */
 int hpmpc_mi355x_kkt_tangent_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi355x_layout *lay, int nprob, int p0,
                                    int count, int ndir, const double *BAbt, const double *RSQrq, const double *DCt,
                                    const double *db, const double *dq, const double *dd, double *dux, double *dpi,
@@ -653,6 +653,52 @@ int hpmpc_mi355x_ocp_tangent_batch(const hpmpc_mi355x_ocp_plan *plan, const hpmp
                                    int p0, int count, int ndir, const double *BAbt, const double *RSQrq,
                                    const double *DCt, double *du, double *dx, double *dpi, double *dlam, double *dt,
                                    const double *ws, double *scratch, int compute_mult, void *stream);
+
+/* ---- the KKT adjoint solve: reverse-mode sensitivities of the re-solve, one set per scalar loss ----
+ * The transpose of the tangent map T above.  For cotangents (gux, gpi, glam, gt) of the re-solved (ux, pi, lam, t) --
+ * the gradient of a scalar loss with respect to the iterate -- the call returns (bbar, qbar, dbar) = T' g, that loss's
+ * gradient with respect to every element of b, q / r and the bounds d, in ONE Riccati solve on the persisted factor
+ * where forward mode takes one per parameter direction; e.g. d u_0 / d x_0 from nu[0] sets (cotangent e_i on u_0)
+ * instead of nx0 tangent sets.  With w = lam * t^-1 on every [lb | ub | lg | ug] slot and C the constraint rows:
+ *   h = gt - w glam,  c_j = h_lo - h_up;   (y_ux, y_pi) = S(gux + C' c, gpi), S the tangent's Riccati solve;
+ *   qbar = y_ux,  bbar = y_pi,  z = C y_ux,  dbar_lo = -h_lo - w_lo z,  dbar_up = h_up - w_up z.
+ * S is minus the inverse of the symmetric KKT matrix, so this is T' exactly in exact arithmetic.  Where the
+ * reference's x-pivot clamp fired on a stage, the persisted factor is not that of a symmetric system and the call is
+ * DEFINED as the three steps above, not as an exact transpose.  It is exactly linear: zero cotangents give zeros and
+ * cotangents scaled by a power of two give the scaled result bit for bit.
+ * Every problem takes nadj cotangent sets; set s = p * nadj + r belongs to problem p.  One launch, one wavefront per
+ * set.  Layouts are the tangent's: gux / qbar 16 doubles per stage in variable order, gpi / bbar 16 in state order,
+ * glam / gt / dbar 32 as [lb | ub | lg | ug], nprob * nadj sets of each.  Any cotangent may be null: zero.  qbar and
+ * dbar are required; every element of them (and of bbar) in the sets in range is written, padding as zeros.  A null
+ * bbar skips the multiplier half of the solve and nothing of b's is written.
+ * Which ws is valid: exactly what is valid for hpmpc_mi355x_kkt_new_rhs_batch (an IPM of the same problems with
+ * kk >= 1; not a queue solve).  Of it the call reads the factor, t^-1 and the multiplier backup; it never writes ws
+ * (nor BAbt, RSQrq, DCt, the cotangents), so adjoints, tangents and re-solves may follow one IPM in any number and
+ * order.  Takes tile plans with ng > 0 and layouts like the re-solve.  scratch: nprob * nadj *
+ * hpmpc_mi355x_kkt_scratch_doubles(plan) doubles, no initialisation needed and no result depends on its contents.
+ * Asynchronous on `stream`, synchronises with nothing; only the sets of problems [p0, p0+count) are read or written;
+ * count = 0 returns 0.  nadj < 1, a bad range, a null required pointer, a null DCt with ng > 0 or a refused launch
+ * return HPMPC_MI355X_EUNSUPPORTED and write nothing.
+ * Out of scope, absent rather than half-built: gradients with respect to the matrices (A, B, Q, S, R, C, D) -- they
+ * are outer products of the adjoint solution with the base iterate and belong in a later change; a
+ * torch.autograd.Function; an adjoint of the IPM iteration itself; soft-constraint and wide-stage plans. */
+int hpmpc_mi355x_kkt_adjoint_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi355x_layout *lay, int nprob, int p0,
+                                   int count, int nadj, const double *BAbt, const double *RSQrq, const double *DCt,
+                                   const double *gux, const double *gpi, const double *glam, const double *gt,
+                                   double *bbar, double *qbar, double *dbar, const double *ws, double *scratch,
+                                   void *stream);
+/* The same for dense cotangents and dense gradients on an OCP plan (packed default layout).  gu shaped like r, gx
+ * like q, gpi like b, glam / gt compact as [lb nb | ub nb | lg ng | ug ng]: (nprob, nadj, size) with the per-problem
+ * sizes of hpmpc_mi355x_ocp_sizes [23..26]; a null one is zero.  The gradients gb, gq, gr, glb, gub, glg, gug have the
+ * shapes of the dense data arrays, (nprob, nadj, size) with the sizes at [2], [6], [7], [8], [9], [12], [13]; a null
+ * one is not wanted, at least one is required, and a null gb skips the multiplier half of the solve.  The placements
+ * are the exact transposes of the dense tangent call's (the equality-box fix is not part of either), and they are
+ * the prologue and epilogue of the one kernel launch.  scratch as above. */
+int hpmpc_mi355x_ocp_adjoint_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, int p0, int count, int nadj,
+                                   const double *BAbt, const double *RSQrq, const double *DCt, const double *gu,
+                                   const double *gx, const double *gpi, const double *glam, const double *gt,
+                                   double *gb, double *gq, double *gr, double *glb, double *gub, double *glg,
+                                   double *gug, const double *ws, double *scratch, void *stream);
 
 #ifdef __cplusplus
 }

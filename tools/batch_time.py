@@ -1,4 +1,4 @@
-"""What tools/ocp_batch_time.py, kkt_batch_time.py and kkt_tangent_time.py share: the batch they time, the event
+"""What tools/ocp_batch_time.py, kkt_batch_time.py, kkt_tangent_time.py and kkt_adjoint_time.py share: the batch they time, the event
 timers and the one-JSON-line output.
 
 Batch: `nprob` problems of N=100, nx=12, nu=4 (nx[0] = 0) with 4 input and 6 state boxes per stage, from
