@@ -65,6 +65,8 @@ _SIG = dict(
     ocp_tangent_batch="i:ppiiiippppppppppip",
     kkt_adjoint_batch="i:ppiiiippppppppppppp",
     ocp_adjoint_batch="i:piiiipppppppppppppppppp",
+    ocp_matrix_grads_batch="i:piiiipppppppp",
+    ocp_adjoint_data_batch="i:piiiippppppppppppppp",
 )
 # {function name: (restype, argtypes)}
 SIGNATURES = {"hpmpc_mi355x_" + n: (_CTYPE[s[0]], [_CTYPE[c] for c in s[2:]]) for n, s in _SIG.items()}

@@ -13,6 +13,7 @@ struct SoftResArgs;
 struct WideIpmArgs;
 struct TanArgs;
 struct AdjArgs;
+struct MatGradArgs;
 struct OcpPackArgs;
 struct OcpUnpackArgs;
 
@@ -34,6 +35,8 @@ int hk_kkt_rhs_launch(const KArgs* a, const KktArgs* x, int count, hipStream_t s
 int hk_kkt_tan_launch(const KArgs* a, const TanArgs* x, int count, hipStream_t stream);
 // hk_adj.hip: the batched KKT adjoint solve, x->k.nrhs cotangent sets for each of `count` problems in one launch
 int hk_kkt_adj_launch(const KArgs* a, const AdjArgs* x, int count, hipStream_t stream);
+// hk_matgrad.hip: the OCP matrix gradients, one workgroup per (stage, set) of a->count * a->nadj sets in one launch
+int hk_ocp_matgrad_launch(const MatGradArgs* a, hipStream_t stream);
 // hk_wide.hip (which: HkWideLaunch; args: the WideArgs / PcArgs / PxArgs of that kernel) and hk_wide_ipm.hip
 int hk_wide_launch(int which, const void* args, int count, int lds_doubles, hipStream_t stream);
 int hk_wide_ipm_launch(const WideIpmArgs* a, int count, int lds_doubles, hipStream_t stream);

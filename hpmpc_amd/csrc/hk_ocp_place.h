@@ -1,7 +1,7 @@
 // hk_ocp_place.h -- where the OCP front end's dense vectors sit in the solver's padded stage vectors, and back: one
 // definition of each placement for hk_ocp_pack, hk_ocp_pack_vectors, hk_ocp_unpack (hk_ocp.hip) and the dense prologue
-// and epilogue of hk_kkt_tan (hk_tan.hip), and the transposes of both for those of hk_kkt_adj (hk_adj.hip).  Device code
-// only; lane l of a wavefront owns one element.
+// and epilogue of hk_kkt_tan (hk_tan.hip), the transposes of both for those of hk_kkt_adj (hk_adj.hip), and the slots
+// hk_ocp_matgrad (hk_matgrad.hip) reads by dense index.  Device code only; lane l of a wavefront owns one element.
 //
 // In: stage k's seed row, 64 doubles -- lanes 0..15 b_k (state order), 16..31 [r_k | q_k] (variable order), 32..63 d_k =
 // [lb pnb | ub pnb | lg png | ug png]; and the warm start ux_k = [u0_k | x0_k | 0 ..].
@@ -157,5 +157,12 @@ __device__ __forceinline__ void ocp_grad_store(const OcpStage& s, const OcpGrads
         if (o.ug && ch >= 0 && ch < s.ng) o.ug[s.dn[OCP_ug] + ch] = v;
     }
 }
+
+// ---- by dense index (hk_ocp_matgrad, hk_matgrad.hip): the slot of input j / state j in the V16 stage vector in
+// variable order [u | x], and of general constraint l's lower / upper side in the V32 stage vector ----
+__device__ __forceinline__ int ocp_slot_u(const OcpStage&, int j) { return j; }
+__device__ __forceinline__ int ocp_slot_x(const OcpStage& s, int j) { return s.nu + j; }
+__device__ __forceinline__ int ocp_slot_lg(const OcpStage& s, int l) { return 2 * s.pnb + l; }
+__device__ __forceinline__ int ocp_slot_ug(const OcpStage& s, int l) { return 2 * s.pnb + s.png + l; }
 
 }  // namespace

@@ -5,10 +5,13 @@
 // directions and results, the re-solve's layouts) and hpmpc_mi355x_ocp_tangent_batch (dense directions and results on
 // an OCP plan), ndir direction sets per problem (hk_kkt_tan, hk_tan.hip); and that tangent's transpose, the KKT adjoint
 // solve hpmpc_mi355x_kkt_adjoint_batch / hpmpc_mi355x_ocp_adjoint_batch, nadj cotangent sets per problem (hk_kkt_adj,
-// hk_adj.hip).  The workspaces an IPM left (hpmpc_mi355x_ipm_batch, _ipm_solo, _ocp_ipm_batch) are read only; each
-// set's work vectors live in the caller's scratch (kkt_scratch_doubles, hk_kkt_args.h).  The core calls carry a DCt
-// array, so they take tile plans with general constraints (batch_args with DCT_ARRAY).
+// hk_adj.hip), and on its solution the gradients with respect to the dense matrices,
+// hpmpc_mi355x_ocp_matrix_grads_batch / hpmpc_mi355x_ocp_adjoint_data_batch (hk_ocp_matgrad, hk_matgrad.hip).  The
+// workspaces an IPM left (hpmpc_mi355x_ipm_batch, _ipm_solo, _ocp_ipm_batch) are read only; each set's work vectors
+// live in the caller's scratch (kkt_scratch_doubles, hk_kkt_args.h).  The core calls carry a DCt array, so they take
+// tile plans with general constraints (batch_args with DCT_ARRAY).
 #include "hk_adj_args.h"
+#include "hk_matgrad_args.h"
 #include "hk_ocp_plan.h"
 #include "hk_tan_args.h"
 
@@ -164,24 +167,22 @@ extern "C" int hpmpc_mi355x_kkt_adjoint_batch(const hpmpc_mi355x_plan* plan, con
     return g_err = 0;
 }
 
-extern "C" int hpmpc_mi355x_ocp_adjoint_batch(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nadj,
-                                              const double* BAbt, const double* RSQrq, const double* DCt,
-                                              const double* gu, const double* gx, const double* gpi,
-                                              const double* glam, const double* gt, double* gb, double* gq, double* gr,
-                                              double* glb, double* gub, double* glg, double* gug, const double* ws,
-                                              double* scratch, void* stream) {
-    if (!O) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_adjoint_batch: plan");
-        return g_err;
-    }
-    KArgs a;
-    AdjArgs x;
+namespace {
+
+constexpr bool ocp_is_vector(int i) {
+    return i == OCP_b || i == OCP_q || i == OCP_r || i == OCP_lb || i == OCP_ub || i == OCP_lg || i == OCP_ug;
+}
+
+// The checks and argument blocks of the dense adjoint launch, shared by hpmpc_mi355x_ocp_adjoint_batch and
+// hpmpc_mi355x_ocp_adjoint_data_batch.  want: the vector gradients (a matrix entry is not looked at); any: the call has
+// an output; mult: the multiplier half of the solve runs.  False as for sets_args.
+bool ocp_adjoint_args(KArgs& a, AdjArgs& x, const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nadj,
+                      const double* BAbt, const double* RSQrq, const double* DCt, const double* const cot[5],
+                      const OcpGrad& want, bool any, bool mult, const double* ws, double* scratch, const char* who) {
     memset(&x, 0, sizeof x);
-    const bool any = gb || gq || gr || glb || gub || glg || gug;
-    if (!sets_args(a, x.k, O->tile.get(), nullptr, nprob, p0, count, nadj, BAbt, RSQrq, DCt, ws, scratch, any,
-                   gb && O->dense[OCP_b] > 0, "hpmpc_mi355x_ocp_adjoint_batch", "hpmpc_mi355x adjoint call: nadj"))
-        return g_err;
-    const double* cot[5] = {gu, gx, gpi, glam, gt};
+    if (!sets_args(a, x.k, O->tile.get(), nullptr, nprob, p0, count, nadj, BAbt, RSQrq, DCt, ws, scratch, any, mult,
+                   who, "hpmpc_mi355x adjoint call: nadj"))
+        return false;
     const long long scot[5] = {O->su, O->sx, O->sp, O->sl, O->sl};
     for (int i = 0; i < 5; i++) {
         if (scot[i] > 0) {  // a cotangent the plan has no element of is never read
@@ -189,18 +190,178 @@ extern "C" int hpmpc_mi355x_ocp_adjoint_batch(const hpmpc_mi355x_ocp_plan* O, in
             x.cot[i].s = scot[i];
         }
     }
+    for (int i = 0; i < OCP_NARR; i++) {
+        if (ocp_is_vector(i) && O->dense[i] > 0) {
+            x.grad.p[i] = want.p[i];
+            x.grad.s[i] = want.s[i];
+        }
+    }
+    x.ost = O->d_st.get();
+    return true;
+}
+
+// The matrix entries of `grads` and the arrays they need -> m.  bbar / qbar / dbar and their strides are the caller's
+// to set.  False: refused, g_err set.
+bool matgrad_args(MatGradArgs& m, const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nadj,
+                  const double* ux, const double* pi, const double* lam, const hpmpc_mi355x_ocp_grads* grads,
+                  const char* who) {
+    memset(&m, 0, sizeof m);
+    bool ab = false, cd = false;
+    for (int i = 0; i < OCP_NARR; i++) {
+        if (ocp_is_vector(i) || !grads->ptr[i]) continue;
+        if (grads->stride[i] < O->dense[i]) {
+            hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x matrix gradients: a stride below the array's size");
+            return false;
+        }
+        if (O->dense[i] == 0) continue;  // a matrix the plan has no element of is never written
+        m.grad.p[i] = grads->ptr[i];
+        m.grad.s[i] = grads->stride[i];
+        ab = ab || i == OCP_A || i == OCP_B;
+        cd = cd || i == OCP_C || i == OCP_D;
+    }
+    if (!ux || (ab && !pi) || (cd && !lam)) {
+        null_array(who);
+        return false;
+    }
+    const long long n1 = O->N + 1;
+    m.N = O->N;
+    m.nprob = nprob;
+    m.p0 = p0;
+    m.count = count;
+    m.nadj = nadj;
+    m.row_major = O->row_major;
+    m.st = O->d_st.get();
+    m.ux = ux;
+    m.pi = ab ? pi : nullptr;
+    m.lam = cd ? lam : nullptr;
+    m.sV16 = n1 * V16;
+    m.sV32 = n1 * V32;
+    return true;
+}
+
+bool wants_matrix(const hpmpc_mi355x_ocp_grads* g) {
+    for (int i = 0; i < OCP_NARR; i++)
+        if (!ocp_is_vector(i) && g->ptr[i]) return true;
+    return false;
+}
+
+bool no_plan(const void* O, const char* who) {
+    if (O) return false;
+    hk_set_error(HPMPC_MI355X_EUNSUPPORTED, who);
+    return true;
+}
+
+}  // namespace
+
+extern "C" int hpmpc_mi355x_ocp_adjoint_batch(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nadj,
+                                              const double* BAbt, const double* RSQrq, const double* DCt,
+                                              const double* gu, const double* gx, const double* gpi,
+                                              const double* glam, const double* gt, double* gb, double* gq, double* gr,
+                                              double* glb, double* gub, double* glg, double* gug, const double* ws,
+                                              double* scratch, void* stream) {
+    if (no_plan(O, "hpmpc_mi355x_ocp_adjoint_batch: plan")) return g_err;
+    KArgs a;
+    AdjArgs x;
+    const double* cot[5] = {gu, gx, gpi, glam, gt};
+    OcpGrad want;
+    memset(&want, 0, sizeof want);
     const struct {
         int i;
         double* p;
     } grads[] = {{OCP_b, gb}, {OCP_q, gq}, {OCP_r, gr}, {OCP_lb, glb}, {OCP_ub, gub}, {OCP_lg, glg}, {OCP_ug, gug}};
+    bool any = false;
     for (const auto& g : grads) {
-        if (O->dense[g.i] > 0) {
-            x.grad.p[g.i] = g.p;
-            x.grad.s[g.i] = O->dense[g.i];
-        }
+        want.p[g.i] = g.p;
+        want.s[g.i] = O->dense[g.i];
+        any = any || g.p;
     }
-    x.ost = O->d_st.get();
+    if (!ocp_adjoint_args(a, x, O, nprob, p0, count, nadj, BAbt, RSQrq, DCt, cot, want, any, gb && O->dense[OCP_b] > 0,
+                          ws, scratch, "hpmpc_mi355x_ocp_adjoint_batch"))
+        return g_err;
     if (const int e = hk_kkt_adj_launch(&a, &x, count, (hipStream_t)stream))
         return launch_error(e, "hk_kkt_adj launch failed");
+    return g_err = 0;
+}
+
+extern "C" int hpmpc_mi355x_ocp_matrix_grads_batch(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count,
+                                                   int nadj, const double* ux, const double* pi, const double* lam,
+                                                   const double* bbar, const double* qbar, const double* dbar,
+                                                   const hpmpc_mi355x_ocp_grads* grads, void* stream) {
+    const char* who = "hpmpc_mi355x_ocp_matrix_grads_batch";
+    if (no_plan(O, "hpmpc_mi355x_ocp_matrix_grads_batch: plan")) return g_err;
+    g_err = 0;
+    if (!range_ok(O, nprob, p0, count, who) || !sets_ok(nprob, nadj, "hpmpc_mi355x adjoint call: nadj") || count == 0)
+        return g_err;
+    if (!grads || !qbar) return null_array(who);
+    for (int i = 0; i < OCP_NARR; i++) {
+        if (ocp_is_vector(i) && grads->ptr[i]) {
+            hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_matrix_grads_batch: vector gradients (b, q, r, "
+                                                    "lb, ub, lg, ug) are the adjoint call's");
+            return g_err;
+        }
+    }
+    if (!wants_matrix(grads)) return null_array(who);
+    MatGradArgs m;
+    if (!matgrad_args(m, O, nprob, p0, count, nadj, ux, pi, lam, grads, who)) return g_err;
+    if ((m.pi && !bbar) || (m.lam && !dbar)) return null_array(who);
+    m.qbar = qbar;
+    m.bbar = m.pi ? bbar : nullptr;
+    m.dbar = m.lam ? dbar : nullptr;
+    m.sq = m.sb = m.sV16;
+    m.sd = m.sV32;
+    if (const int e = hk_ocp_matgrad_launch(&m, (hipStream_t)stream))
+        return launch_error(e, "hk_ocp_matgrad launch failed");
+    return g_err = 0;
+}
+
+extern "C" int hpmpc_mi355x_ocp_adjoint_data_batch(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count,
+                                                   int nadj, const double* BAbt, const double* RSQrq,
+                                                   const double* DCt, const double* ux, const double* pi,
+                                                   const double* lam, const double* gu, const double* gx,
+                                                   const double* gpi, const double* glam, const double* gt,
+                                                   const hpmpc_mi355x_ocp_grads* grads, const double* ws,
+                                                   double* scratch, void* stream) {
+    const char* who = "hpmpc_mi355x_ocp_adjoint_data_batch";
+    if (no_plan(O, "hpmpc_mi355x_ocp_adjoint_data_batch: plan")) return g_err;
+    KArgs a;
+    AdjArgs x;
+    const double* cot[5] = {gu, gx, gpi, glam, gt};
+    OcpGrad want;
+    memset(&want, 0, sizeof want);
+    bool any = false, mult = false, bad_stride = false;
+    if (grads) {
+        for (int i = 0; i < OCP_NARR; i++) {
+            any = any || grads->ptr[i];
+            if (!grads->ptr[i]) continue;
+            if (ocp_is_vector(i)) {
+                want.p[i] = grads->ptr[i];
+                want.s[i] = grads->stride[i];
+                bad_stride = bad_stride || grads->stride[i] < O->dense[i];
+            }
+            mult = mult || ((i == OCP_b || i == OCP_A || i == OCP_B) && O->dense[i] > 0);
+        }
+    }
+    if (!ocp_adjoint_args(a, x, O, nprob, p0, count, nadj, BAbt, RSQrq, DCt, cot, want, any, mult, ws, scratch, who))
+        return g_err;
+    if (bad_stride) {
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_adjoint_data_batch: a stride below the array's size");
+        return g_err;
+    }
+    // every check of the second launch comes before the first
+    MatGradArgs m;
+    const bool mats = grads && wants_matrix(grads);
+    if (mats) {
+        if (!matgrad_args(m, O, nprob, p0, count, nadj, ux, pi, lam, grads, who)) return g_err;
+        const KktSet c = carve_set(scratch, O->N);  // where hk_kkt_adj leaves the dense call's qbar, bbar, dbar
+        m.qbar = c.dux;
+        m.bbar = m.pi ? c.dpi : nullptr;
+        m.dbar = m.lam ? c.res_d : nullptr;
+        m.sq = m.sb = m.sd = x.k.sS;
+    }
+    if (const int e = hk_kkt_adj_launch(&a, &x, count, (hipStream_t)stream))
+        return launch_error(e, "hk_kkt_adj launch failed");
+    if (mats)
+        if (const int e = hk_ocp_matgrad_launch(&m, (hipStream_t)stream))
+            return launch_error(e, "hk_ocp_matgrad launch failed");
     return g_err = 0;
 }

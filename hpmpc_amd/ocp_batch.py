@@ -134,6 +134,7 @@ def kkt_set_arrays(problems):
 
 
 VEC_KEYS = ("b", "q", "r", "lb", "ub", "lg", "ug")  # the dense arrays a tangent direction may have
+MAT_KEYS = ("A", "B", "Q", "S", "R", "C", "D")  # the others: gradients only (matrix_gradients, adjoint_data)
 
 
 def tangent_set_arrays(problem_deltas):
@@ -211,6 +212,10 @@ class _OcpData(C.Structure):
     _fields_ = [("ptr", C.c_void_p * len(KEYS)), ("stride", C.c_longlong * len(KEYS))]
 
 
+class _OcpGrads(C.Structure):
+    _fields_ = [("ptr", C.c_void_p * len(KEYS)), ("stride", C.c_longlong * len(KEYS))]
+
+
 ocp_lib = lib  # the hpmpc_mi355x_ocp_* calls are bound with every other one (hpmpc_amd.bindings)
 
 
@@ -226,7 +231,8 @@ def ocp_plan_create(N, nx, nu, nb, idxb, ng, order="C"):
 class OcpBatchSolver:
     """``nprob`` OCPs with the given stage sizes: owns the lib4 arrays, the iterate, the workspaces and the outputs
     (torch tensors on ``device``).  pack() -> solve() -> finish(), then any number of resolve() -> finish() or
-    kkt_sets() / tangent() / adjoint() on the factor solve() left, all asynchronous on torch's current stream.
+    kkt_sets() / tangent() / adjoint() / adjoint_data() on the factor solve() left, all asynchronous on torch's current
+    stream.
     There is no CPU fallback: without a GPU or the built library the constructor raises."""
 
     def __init__(self, N, nx, nu, nb, idxb, ng, nprob, order="C", device="cuda", k_max=50):
@@ -482,20 +488,9 @@ class OcpBatchSolver:
             bufs[nadj] = {key: new(self.sizes[key]) for key in VEC_KEYS}
         return bufs[nadj]
 
-    def adjoint(self, cot, nadj, p0=0, count=None, want=VEC_KEYS):
-        """Reverse sensitivities of the re-solved plan (hpmpc_mi355x_ocp_adjoint_batch), the transpose of tangent():
-        for ``nadj`` cotangent sets per problem -- each the gradient of a scalar loss with respect to what resolve()
-        computes -- that loss's gradient with respect to b, q, r and the bounds, one Riccati solve per set on the
-        factor of solve().  ``cot``: {key: contiguous float64 device tensor (nprob, nadj, size)} for any of u, x, pi,
-        lam, t (the sizes of the outputs; lam / t compact); a missing (or None) key is zero.  Returns {key: (nprob,
-        nadj, sizes[key])} over ``want`` (default all of b, q, r, lb, ub, lg, ug) -- tensors of grad_buffers(nadj);
-        a key left out of ``want`` is not written, and without "b" the multiplier half of the solve is skipped.
-        Neither ws nor the solver's data or iterate is written."""
-        torch = self.torch
-        p0, count = self._range(p0, count)
-        if not want or any(key not in VEC_KEYS for key in want):
-            raise ValueError(f"want: a non-empty subset of {VEC_KEYS} expected")
-        s = self.sizes
+    def _cot_ptrs(self, cot, nadj):
+        """The pointers gu, gx, gpi, glam, gt of the dense cotangents ``cot`` (None: zero), after checking them."""
+        torch, s = self.torch, self.sizes
         size = dict(u=s["u"], x=s["x"], pi=s["pi_out"], lam=s["lam_out"], t=s["lam_out"])
         ptrs = []
         for key in OUT_KEYS:
@@ -507,6 +502,22 @@ class OcpBatchSolver:
             ptrs.append(None if x is None else x.data_ptr())
         if any(key not in OUT_KEYS for key in cot):
             raise ValueError(f"cotangents are keyed by {OUT_KEYS}")
+        return ptrs
+
+    def adjoint(self, cot, nadj, p0=0, count=None, want=VEC_KEYS):
+        """Reverse sensitivities of the re-solved plan (hpmpc_mi355x_ocp_adjoint_batch), the transpose of tangent():
+        for ``nadj`` cotangent sets per problem -- each the gradient of a scalar loss with respect to what resolve()
+        computes -- that loss's gradient with respect to b, q, r and the bounds, one Riccati solve per set on the
+        factor of solve().  ``cot``: {key: contiguous float64 device tensor (nprob, nadj, size)} for any of u, x, pi,
+        lam, t (the sizes of the outputs; lam / t compact); a missing (or None) key is zero.  Returns {key: (nprob,
+        nadj, sizes[key])} over ``want`` (default all of b, q, r, lb, ub, lg, ug) -- tensors of grad_buffers(nadj);
+        a key left out of ``want`` is not written, and without "b" the multiplier half of the solve is skipped.
+        Neither ws nor the solver's data or iterate is written."""
+        p0, count = self._range(p0, count)
+        if not want or any(key not in VEC_KEYS for key in want):
+            raise ValueError(f"want: a non-empty subset of {VEC_KEYS} expected")
+        s = self.sizes
+        ptrs = self._cot_ptrs(cot, nadj)
         g = self.grad_buffers(nadj)
         check(lib().hpmpc_mi355x_ocp_adjoint_batch(
             self.plan, self.nprob, p0, count, nadj, *self._lib4(), *ptrs,
@@ -528,6 +539,89 @@ class OcpBatchSolver:
                                count, nadj, *self._lib4(ptr=False), gux, gpi, glam, gt, out, self.ws, want_b,
                                self._stream()), "hpmpc_mi355x_kkt_adjoint_batch")
         return (out["pi"] if want_b else None), out["ux"], out["lam"]
+
+    def matrix_grad_buffers(self, nadj: int = 1) -> dict:
+        """The dense per-set gradient tensors A, B, Q, S, R, C, D of shape (nprob, nadj, max(size, 1)) that
+        matrix_gradients(nadj=nadj) and adjoint_data(nadj=nadj) write (allocated on first use, then reused and
+        overwritten)."""
+        if nadj < 1:
+            raise ValueError("at least one set per problem expected")
+        bufs = self.__dict__.setdefault("_mgrads", {})
+        if nadj not in bufs:
+            new = lambda n: self.torch.zeros((self.nprob, nadj, max(n, 1)), dtype=self.torch.float64, device=self.dev)
+            bufs[nadj] = {key: new(self.sizes[key]) for key in MAT_KEYS}
+        return bufs[nadj]
+
+    def _grads_struct(self, bufs, want):
+        """hpmpc_mi355x_ocp_grads over the tensors ``bufs`` (nprob, nadj, >= size): the keys of ``want``, else null."""
+        gs = _OcpGrads()
+        for i, key in enumerate(KEYS):
+            gs.ptr[i], gs.stride[i] = (bufs[key].data_ptr(), bufs[key].shape[-1]) if key in want else (None, 0)
+        return gs
+
+    def _base_ptrs(self, base):
+        """Pointers of the padded base iterate ux, pi, lam: the solver's own (the raw iterate solve() or resolve() left,
+        without finish()'s equality-box fix), or ``base`` = dict(ux=, pi=, lam=) of (nprob, sizes[key]) tensors."""
+        if base is None:
+            return self.ux.data_ptr(), self.pi.data_ptr(), self.lam.data_ptr()
+        out = []
+        for key in ("ux", "pi", "lam"):
+            x = base[key]
+            if x.dtype != self.torch.float64 or x.device.type != self.dev.type or not x.is_contiguous() or \
+                    tuple(x.shape) != (self.nprob, self.sizes[key]):
+                raise ValueError(f"base {key}: contiguous float64 tensor ({self.nprob}, {self.sizes[key]}) on "
+                                 f"{self.dev} expected")
+            out.append(x.data_ptr())
+        return tuple(out)
+
+    def matrix_gradients(self, bbar, qbar, dbar, nadj, want=MAT_KEYS, base=None, p0=0, count=None):
+        """Gradients with respect to the matrices from an adjoint solution (hpmpc_mi355x_ocp_matrix_grads_batch, one
+        launch): bbar, qbar (nprob, nadj, N+1, 16), dbar (nprob, nadj, N+1, 32) as adjoint_sets returns them (bbar may
+        be None without "A" and "B"), and the base iterate (``base``, default the solver's own ux, pi, lam).  Per stage
+        gA = bbar x' + pi qxbar', gB = bbar u' + pi rbar', gQ = (qxbar x' + x qxbar') / 2, gR = (rbar u' + u rbar') / 2,
+        gS = rbar x' + u qxbar', gC = w qxbar' - s x', gD = w rbar' - s u' with w = lam_ug - lam_lg, s = dbar_lg +
+        dbar_ug; gQ / gR are the gradients for symmetric perturbations.  This is the transpose of the linearised KKT
+        system on the persisted factor, not the derivative of a fully converged solve (include/hpmpc_mi355x.h).
+        Returns {key: (nprob, nadj, sizes[key])} over ``want`` -- tensors of matrix_grad_buffers(nadj); blocks in the
+        solver's order ("C" row-major / "F" column-major).  No input is written."""
+        torch = self.torch
+        p0, count = self._range(p0, count)
+        if not want or any(key not in MAT_KEYS for key in want):
+            raise ValueError(f"want: a non-empty subset of {MAT_KEYS} expected")
+        for name, x, w in (("bbar", bbar, 16), ("qbar", qbar, 16), ("dbar", dbar, 32)):
+            if x is None and name == "bbar" and "A" not in want and "B" not in want:
+                continue
+            if x is None or tuple(x.shape) != (self.nprob, nadj, self.N + 1, w) or x.dtype != torch.float64 or \
+                    x.device.type != self.dev.type or not x.is_contiguous():
+                raise ValueError(f"{name}: contiguous float64 tensor of shape {(self.nprob, nadj, self.N + 1, w)} "
+                                 "expected")
+        g = self.matrix_grad_buffers(nadj)
+        gs = self._grads_struct(g, want)
+        check(lib().hpmpc_mi355x_ocp_matrix_grads_batch(
+            self.plan, self.nprob, p0, count, nadj, *self._base_ptrs(base), None if bbar is None else bbar.data_ptr(),
+            qbar.data_ptr(), dbar.data_ptr(), C.byref(gs), self._stream()), "hpmpc_mi355x_ocp_matrix_grads_batch")
+        return {key: g[key][..., :self.sizes[key]] for key in MAT_KEYS if key in want}
+
+    def adjoint_data(self, cot, nadj, want=KEYS, base=None, p0=0, count=None):
+        """Gradients with respect to any of the fourteen data arrays (hpmpc_mi355x_ocp_adjoint_data_batch): adjoint()'s
+        launch, then matrix_gradients()'s on the adjoint solution in the scratch, on one stream with nothing in
+        between.  ``cot`` as for adjoint(); ``base`` as for matrix_gradients().  Returns {key: (nprob, nadj,
+        sizes[key])} over ``want`` -- the vector keys are tensors of grad_buffers(nadj) and bit for bit adjoint()'s, the
+        matrix keys tensors of matrix_grad_buffers(nadj) and bit for bit adjoint_sets() -> matrix_gradients()'s.
+        Wanting "A" or "B" runs the multiplier half of the solve even without "b"."""
+        p0, count = self._range(p0, count)
+        if not want or any(key not in KEYS for key in want):
+            raise ValueError(f"want: a non-empty subset of {KEYS} expected")
+        ptrs = self._cot_ptrs(cot, nadj)
+        g = dict(self.grad_buffers(nadj))
+        if any(key in MAT_KEYS for key in want):
+            g.update(self.matrix_grad_buffers(nadj))
+        gs = self._grads_struct(g, want)
+        check(lib().hpmpc_mi355x_ocp_adjoint_data_batch(
+            self.plan, self.nprob, p0, count, nadj, *self._lib4(), *self._base_ptrs(base), *ptrs, C.byref(gs),
+            self.ws.data_ptr(), self.kkt_buffers(nadj)["scratch"].data_ptr(), self._stream()),
+            "hpmpc_mi355x_ocp_adjoint_data_batch")
+        return {key: g[key][..., :self.sizes[key]] for key in KEYS if key in want}
 
     def x0_gradient(self, A0, S0, grads):
         """The chain rule of x0_directions: the gradient with respect to an x_0 folded into stage 0 (b_0 = A_0 x_0 + b,

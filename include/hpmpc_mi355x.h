@@ -632,8 +632,9 @@ int hpmpc_mi355x_ocp_unpack_sets(const hpmpc_mi355x_ocp_plan *plan, int nprob, i
  * compute_mult = 0: dpi is returned as zeros.  Asynchronous on `stream`, synchronises with nothing; only the sets of
  * problems [p0, p0+count) are read or written; count = 0 returns 0.  ndir < 1, a bad range, a null required pointer,
  * a null DCt with ng > 0 or a refused launch return HPMPC_MI355X_EUNSUPPORTED and write nothing.
- * Reverse mode is the adjoint solve below.  Out of scope, refused or absent rather than half-built: directions in the
- * matrices (A, B, Q, S, R, C, D), and per-set residual norms. */
+ * Reverse mode is the adjoint solve below, and the gradients with respect to the matrices follow it
+ * (hpmpc_mi355x_ocp_matrix_grads_batch).  Out of scope, refused or absent rather than half-built: DIRECTIONS in the
+ * matrices (A, B, Q, S, R, C, D) for this forward call, and per-set residual norms. */
 int hpmpc_mi355x_kkt_tangent_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi355x_layout *lay, int nprob, int p0,
                                    int count, int ndir, const double *BAbt, const double *RSQrq, const double *DCt,
                                    const double *db, const double *dq, const double *dd, double *dux, double *dpi,
@@ -679,9 +680,10 @@ int hpmpc_mi355x_ocp_tangent_batch(const hpmpc_mi355x_ocp_plan *plan, const hpmp
  * Asynchronous on `stream`, synchronises with nothing; only the sets of problems [p0, p0+count) are read or written;
  * count = 0 returns 0.  nadj < 1, a bad range, a null required pointer, a null DCt with ng > 0 or a refused launch
  * return HPMPC_MI355X_EUNSUPPORTED and write nothing.
- * Out of scope, absent rather than half-built: gradients with respect to the matrices (A, B, Q, S, R, C, D) -- they
- * are outer products of the adjoint solution with the base iterate and belong in a later change; a
- * torch.autograd.Function; an adjoint of the IPM iteration itself; soft-constraint and wide-stage plans. */
+ * Gradients with respect to the matrices (A, B, Q, S, R, C, D) are outer products of this adjoint solution with the
+ * base iterate: hpmpc_mi355x_ocp_matrix_grads_batch / hpmpc_mi355x_ocp_adjoint_data_batch below; the Python package
+ * wraps them in a torch.autograd.Function (hpmpc_amd.ocp_autograd).  Out of scope, absent rather than half-built: an
+ * adjoint of the IPM iteration itself; soft-constraint and wide-stage plans. */
 int hpmpc_mi355x_kkt_adjoint_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi355x_layout *lay, int nprob, int p0,
                                    int count, int nadj, const double *BAbt, const double *RSQrq, const double *DCt,
                                    const double *gux, const double *gpi, const double *glam, const double *gt,
@@ -699,6 +701,60 @@ int hpmpc_mi355x_ocp_adjoint_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob,
                                    const double *gx, const double *gpi, const double *glam, const double *gt,
                                    double *gb, double *gq, double *gr, double *glb, double *gub, double *glg,
                                    double *gug, const double *ws, double *scratch, void *stream);
+
+/* ---- gradients with respect to the matrices A, B, Q, S, R, C, D, from the adjoint solution ----
+ * The residuals of the KKT system (d_res_res_mpc_hard_tv) carry b, q / r and d with unit coefficients and are bilinear
+ * in (matrices, iterate).  At a fixed base iterate z = (ux, pi, lam), with ux_k = [u_k | x_k], a perturbation of the
+ * matrices moves them by
+ *   dr_b[k] = dA_k x_k + dB_k u_k,   dr_q[k] = dRSQ_k ux_k + dBAbt_k pi_k + dDCt_k (lam_ug,k - lam_lg,k),
+ *   dr_d[k] = -(dC_k x_k + dD_k u_k)  on both the lg and the ug slots.
+ * The MATRIX TANGENT is defined as T_M(dtheta) = T(dr_b, dr_q, dr_d) with T the tangent map above, and these calls
+ * return its transpose: with (bbar, qbar = [rbar | qxbar], dbar) = T' g the adjoint solution of a cotangent set, per
+ * stage k, in the dense shapes of hpmpc_mi355x_ocp_data,
+ *   gA_k = bbar_k x_k' + pi_k qxbar_k'                 gB_k = bbar_k u_k' + pi_k rbar_k'
+ *   gQ_k = (qxbar_k x_k' + x_k qxbar_k') / 2           gR_k = (rbar_k u_k' + u_k rbar_k') / 2
+ *   gS_k = rbar_k x_k' + u_k qxbar_k'
+ *   gC_k = w_k qxbar_k' - s_k x_k'                     gD_k = w_k rbar_k' - s_k u_k'
+ * with w_k = lam_ug,k - lam_lg,k and s_k = dbar_lg,k + dbar_ug,k.  Conventions: pi_k is the multiplier of stage k's
+ * dynamics x_{k+1} = A_k x_k + B_k u_k + b_k and has nx[k+1] entries; gQ and gR are the gradients for SYMMETRIC
+ * perturbations -- <gQ, dQ> is the directional derivative for dQ = dQ', the kernels read only the lower triangle of
+ * RSQrq -- and are symmetric bit for bit; S is an ordinary nu x nx block.  Blocks of a time-invariant matrix are not
+ * summed over the stages: the caller sums them.
+ * What the quantity is: the exact transpose of T_M, the linearised KKT system on the persisted factor.  It is NOT the
+ * derivative of a fully converged solve: the factor belongs to the last Newton system of the IPM, which was formed one
+ * iterate before the returned point.  Finite differences of whole IPM solves (mu_tol 1e-10) agree with <G, dtheta> to
+ * between 4e-5 and 2e-3 relative on the test problems.  The vector gradients of the adjoint call rest on the same
+ * factor.  Exactly linear in the cotangent like the adjoint solve.
+ * grads: ptr[i] null: gradient i is not wanted; stride[i]: doubles between consecutive SETS (nprob * nadj of them,
+ * problem-major), at least the array's per-problem size.  Every element of a wanted array of the sets in range is
+ * written, nothing else; no atomics, no initialisation needed. */
+typedef struct {
+    double *ptr[HPMPC_MI355X_OCP_NARRAYS];       /* device pointers; null: not wanted */
+    long long stride[HPMPC_MI355X_OCP_NARRAYS];  /* doubles between SETS */
+} hpmpc_mi355x_ocp_grads;
+/* The core: one launch (hk_ocp_matgrad), one workgroup per (stage, set), from padded arrays.  ux, pi, lam: the base
+ * iterate per problem in the solver's padded layouts (16, 16, 32 doubles per stage) -- the IPM's, or a re-solve's.
+ * bbar, qbar, dbar: the outputs of hpmpc_mi355x_kkt_adjoint_batch, nprob * nadj sets.  ux and qbar are required; pi and
+ * bbar when gA or gB is wanted; lam and dbar when the plan has ng > 0 and gC or gD is wanted.  A non-null vector entry
+ * of grads (b, q, r, lb, ub, lg, ug) is refused.  Asynchronous on `stream`; only the sets of problems [p0, p0+count)
+ * are read or written; count = 0 returns 0.  nadj < 1, a bad range, a null plan, a null required pointer, no wanted entry,
+ * a stride below the array's size or a refused launch return HPMPC_MI355X_EUNSUPPORTED and write nothing. */
+int hpmpc_mi355x_ocp_matrix_grads_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, int p0, int count, int nadj,
+                                        const double *ux, const double *pi, const double *lam, const double *bbar,
+                                        const double *qbar, const double *dbar, const hpmpc_mi355x_ocp_grads *grads,
+                                        void *stream);
+/* Gradients with respect to any of the fourteen data arrays in one call: the launch of hpmpc_mi355x_ocp_adjoint_batch
+ * (dense cotangents gu, gx, gpi, glam, gt as there; the vector entries of grads are its gb, gq, gr, glb, gub, glg, gug
+ * and come out bit for bit the same), then the core launch above on the same stream, reading qbar, bbar and dbar from
+ * each set's scratch block: no padded array of the caller's, no host synchronisation.  ux, pi, lam: the base iterate
+ * as above, required as above when a matrix entry is wanted.  Wanting gA or gB forces the multiplier half of the solve
+ * even when gb is null.  ws and scratch as for the adjoint call.  Refusals as above and as the adjoint call's. */
+int hpmpc_mi355x_ocp_adjoint_data_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, int p0, int count, int nadj,
+                                        const double *BAbt, const double *RSQrq, const double *DCt, const double *ux,
+                                        const double *pi, const double *lam, const double *gu, const double *gx,
+                                        const double *gpi, const double *glam, const double *gt,
+                                        const hpmpc_mi355x_ocp_grads *grads, const double *ws, double *scratch,
+                                        void *stream);
 
 #ifdef __cplusplus
 }
