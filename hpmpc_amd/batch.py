@@ -22,6 +22,7 @@ import os
 import numpy as np
 
 from .bindings import LIBPATH, check, lib, plan_args  # noqa: F401  (tests, tools and bench.py import LIBPATH from here)
+from .device import DeviceSolver, tensor_ptr
 from .ocp import OCPQP
 
 kkt_lib = lib  # the batched KKT re-solve's calls are bound with every other one (hpmpc_amd.bindings)
@@ -119,81 +120,74 @@ def kkt_buffers(torch, dev, plan, N: int, nprob: int, nrhs: int) -> dict:
                 scratch=new(int(lib().hpmpc_mi355x_kkt_scratch_doubles(plan))))
 
 
-def _set_call(fn, names, optional, torch, plan, layout, N, nprob, p0, count, nsets, BAbt, RSQrq, DCt, vecs, out, ws,
-              compute_mult, stream) -> int:
-    """A call with the argument list of hpmpc_mi355x_kkt_new_rhs_batch on torch tensors, after checking the shapes of
-    the per-set arrays ``vecs`` (V16, V16, V32 per stage, called ``names``; None allowed for those in ``optional``) and
-    of ``out`` from kkt_buffers(nsets).  Returns the library's code."""
-    for name, x, w in zip(names, vecs, (16, 16, 32)):
-        if x is None and name in optional:
-            continue
-        if x is None or tuple(x.shape) != (nprob, nsets, N + 1, w) or x.dtype != torch.float64 or not x.is_contiguous():
-            raise ValueError(f"{name}: contiguous float64 tensor of shape {(nprob, nsets, N + 1, w)} expected")
-    for name, w in (("ux", 16), ("pi", 16), ("lam", 32), ("t", 32)):
-        if tuple(out[name].shape) != (nprob, nsets, N + 1, w):
+_OUT_WIDTH = dict(ux=16, pi=16, lam=32, t=32)
+
+
+def _set_call(fn, torch, plan, layout, N, nprob, p0, count, nsets, BAbt, RSQrq, DCt, inputs, outs, out, ws,
+              *tail) -> int:
+    """A call with the argument list the set calls share -- plan, layout, range, nsets, the lib4 arrays, the per-set
+    inputs, the per-set outputs, ws, scratch, then ``tail`` -- on torch tensors.  ``inputs``: rows (name, tensor,
+    width, optional) of (nprob, nsets, N+1, width) tensors on the device of ``ws``, checked by tensor_ptr; ``outs``:
+    the keys of ``out`` (from kkt_buffers(nsets)) in the call's order, None for an output passed as null.  Returns the
+    library's code."""
+    shape, dev = {16: (nprob, nsets, N + 1, 16), 32: (nprob, nsets, N + 1, 32)}, ws.device
+    ins = [tensor_ptr(torch, x, shape[w], dev, name, optional) for name, x, w, optional in inputs]
+    for name in outs:
+        if name is not None and out[name].shape != shape[_OUT_WIDTH[name]]:
             raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={nsets}) expected")
-    ptr = lambda x: None if x is None else x.data_ptr()
-    return fn(plan, layout, nprob, p0, count, nsets, ptr(BAbt), ptr(RSQrq), ptr(DCt), *(ptr(x) for x in vecs),
-              ptr(out["ux"]), ptr(out["pi"]), ptr(out["lam"]), ptr(out["t"]), ptr(ws), ptr(out["scratch"]), compute_mult,
-              stream)
+    return fn(plan, layout, nprob, p0, count, nsets, BAbt.data_ptr(), RSQrq.data_ptr(),
+              None if DCt is None else DCt.data_ptr(), *ins,
+              *[None if name is None else out[name].data_ptr() for name in outs], ws.data_ptr(),
+              out["scratch"].data_ptr(), *tail)
 
 
 def kkt_sets_call(torch, plan, layout, N, nprob, p0, count, nrhs, BAbt, RSQrq, DCt, b, q, d, out, ws, compute_mult,
                   stream) -> int:
-    """hpmpc_mi355x_kkt_new_rhs_batch on torch tensors, after checking the shapes of the per-set arrays: b, q (nprob,
-    nrhs, N+1, 16) or None (the problem's augmented rows), d (nprob, nrhs, N+1, 32), ``out`` from kkt_buffers.
-    Returns the library's code."""
-    return _set_call(lib().hpmpc_mi355x_kkt_new_rhs_batch, ("b", "q", "d"), ("b", "q"), torch, plan, layout, N, nprob,
-                     p0, count, nrhs, BAbt, RSQrq, DCt, (b, q, d), out, ws, compute_mult, stream)
+    """hpmpc_mi355x_kkt_new_rhs_batch on torch tensors, after checking the per-set arrays: b, q (nprob, nrhs, N+1, 16)
+    or None (the problem's augmented rows), d (nprob, nrhs, N+1, 32), ``out`` from kkt_buffers.  Returns the library's
+    code."""
+    return _set_call(lib().hpmpc_mi355x_kkt_new_rhs_batch, torch, plan, layout, N, nprob, p0, count, nrhs, BAbt, RSQrq,
+                     DCt, (("b", b, 16, True), ("q", q, 16, True), ("d", d, 32, False)), ("ux", "pi", "lam", "t"), out,
+                     ws, compute_mult, stream)
 
 
 def kkt_tangent_call(torch, plan, layout, N, nprob, p0, count, ndir, BAbt, RSQrq, DCt, db, dq, dd, out, ws,
                      compute_mult, stream) -> int:
-    """hpmpc_mi355x_kkt_tangent_batch on torch tensors, after checking the shapes of the per-set arrays: db, dq
-    (nprob, ndir, N+1, 16), dd (nprob, ndir, N+1, 32), each or all None (a zero direction); ``out`` from
-    kkt_buffers(ndir), whose ux / pi / lam / t receive dux / dpi / dlam / dt.  Returns the library's code."""
-    return _set_call(lib().hpmpc_mi355x_kkt_tangent_batch, ("db", "dq", "dd"), ("db", "dq", "dd"), torch, plan, layout,
-                     N, nprob, p0, count, ndir, BAbt, RSQrq, DCt, (db, dq, dd), out, ws, compute_mult, stream)
+    """hpmpc_mi355x_kkt_tangent_batch on torch tensors, after checking the per-set arrays: db, dq (nprob, ndir, N+1,
+    16), dd (nprob, ndir, N+1, 32), each or all None (a zero direction); ``out`` from kkt_buffers(ndir), whose ux / pi /
+    lam / t receive dux / dpi / dlam / dt.  Returns the library's code."""
+    return _set_call(lib().hpmpc_mi355x_kkt_tangent_batch, torch, plan, layout, N, nprob, p0, count, ndir, BAbt, RSQrq,
+                     DCt, (("db", db, 16, True), ("dq", dq, 16, True), ("dd", dd, 32, True)), ("ux", "pi", "lam", "t"),
+                     out, ws, compute_mult, stream)
 
 
 def kkt_adjoint_call(torch, plan, layout, N, nprob, p0, count, nadj, BAbt, RSQrq, DCt, gux, gpi, glam, gt, out, ws,
                      want_b, stream) -> int:
-    """hpmpc_mi355x_kkt_adjoint_batch on torch tensors, after checking the shapes of the per-set cotangents: gux, gpi
-    (nprob, nadj, N+1, 16), glam, gt (nprob, nadj, N+1, 32), each or all None (zero); ``out`` from kkt_buffers(nadj),
-    whose pi / ux / lam receive bbar / qbar / dbar (bbar only with ``want_b``; its t is not touched).  Returns the
-    library's code."""
-    for name, x, w in (("gux", gux, 16), ("gpi", gpi, 16), ("glam", glam, 32), ("gt", gt, 32)):
-        if x is not None and (tuple(x.shape) != (nprob, nadj, N + 1, w) or x.dtype != torch.float64 or
-                              not x.is_contiguous()):
-            raise ValueError(f"{name}: contiguous float64 tensor of shape {(nprob, nadj, N + 1, w)} expected")
-    for name, w in (("ux", 16), ("pi", 16), ("lam", 32)):
-        if tuple(out[name].shape) != (nprob, nadj, N + 1, w):
-            raise ValueError(f"out[{name!r}]: buffers of kkt_buffers(nrhs={nadj}) expected")
-    ptr = lambda x: None if x is None else x.data_ptr()
-    return lib().hpmpc_mi355x_kkt_adjoint_batch(
-        plan, layout, nprob, p0, count, nadj, ptr(BAbt), ptr(RSQrq), ptr(DCt), ptr(gux), ptr(gpi), ptr(glam), ptr(gt),
-        ptr(out["pi"]) if want_b else None, ptr(out["ux"]), ptr(out["lam"]), ptr(ws), ptr(out["scratch"]), stream)
+    """hpmpc_mi355x_kkt_adjoint_batch on torch tensors, after checking the per-set cotangents: gux, gpi (nprob, nadj,
+    N+1, 16), glam, gt (nprob, nadj, N+1, 32), each or all None (zero); ``out`` from kkt_buffers(nadj), whose pi / ux /
+    lam receive bbar / qbar / dbar (bbar only with ``want_b``; its t is not touched).  Returns the library's code."""
+    return _set_call(lib().hpmpc_mi355x_kkt_adjoint_batch, torch, plan, layout, N, nprob, p0, count, nadj, BAbt, RSQrq,
+                     DCt, (("gux", gux, 16, True), ("gpi", gpi, 16, True), ("glam", glam, 32, True),
+                           ("gt", gt, 32, True)), ("pi" if want_b else None, "ux", "lam"), out, ws, stream)
 
 
-class BatchSolver:
+class BatchSolver(DeviceSolver):
     """Device-resident batch of OCP QPs + the batched HPMPC entry points.
 
     ``nprob`` given: the batch's data are not uploaded from ``qp`` (which then only supplies stage sizes and
     idxb); BAbt / RSQrq / d are allocated for ``nprob`` problems and filled by the caller, e.g. by the rank-0
     scatter of hpmpc_amd.shard."""
 
-    def __init__(self, qp: OCPQP, device="cuda", k_max: int = 50, nprob: int | None = None, aliased: bool = False):
-        import torch
+    _destroy = "hpmpc_mi355x_plan_destroy"
 
-        if not torch.cuda.is_available():
-            raise RuntimeError("BatchSolver needs a GPU (HIP device); there is no CPU fallback")
+    def __init__(self, qp: OCPQP, device="cuda", k_max: int = 50, nprob: int | None = None, aliased: bool = False):
+        super().__init__(device)
         assert nprob is not None or qp.batch is not None, "BatchSolver takes a batched OCPQP"
-        self.torch = torch
+        torch = self.torch
         self.qp = qp
         self.N = N = qp.N
         self.nprob = qp.batch if nprob is None else int(nprob)
         self.k_max = k_max
-        self.dev = torch.device(device)
         L = lib()
         (nx, nu, nb, ng), idxp, self._keep = plan_args(qp.idxb, qp.nx, qp.nu, qp.nb, qp.ng)
         self.plan = L.hpmpc_mi355x_plan_create(N, nx, nu, nb, idxp, ng)
@@ -241,16 +235,6 @@ class BatchSolver:
         self.ret = torch.zeros(P, dtype=torch.int32, device=self.dev)
         self.stat = torch.zeros((P, 5 * k_max), dtype=f64, device=self.dev)
 
-    def __del__(self):
-        try:
-            if getattr(self, "plan", None):
-                lib().hpmpc_mi355x_plan_destroy(self.plan)
-        except Exception:
-            pass
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
-
     def _ipm(self, name, p0, count, opts, *tail):
         """hpmpc_mi355x_<name> on problems [p0, p0 + count) with the arguments every batched IPM call shares
         (opts: mu0, mu_tol, alpha_min, warm_start, compute_mult), then ``tail`` and torch's current stream."""
@@ -272,12 +256,7 @@ class BatchSolver:
 
     def kkt_buffers(self, nrhs: int = 1) -> dict:
         """The output and scratch tensors kkt_new_rhs(nrhs=nrhs) writes (allocated on first use, then reused)."""
-        if nrhs < 1:
-            raise ValueError("nrhs >= 1 expected")
-        bufs = self.__dict__.setdefault("_kkt", {})
-        if nrhs not in bufs:
-            bufs[nrhs] = kkt_buffers(self.torch, self.dev, self.plan, self.N, self.nprob, nrhs)
-        return bufs[nrhs]
+        return self._per_set("kkt", nrhs, lambda n: kkt_buffers(self.torch, self.dev, self.plan, self.N, self.nprob, n))
 
     def kkt_new_rhs(self, b, q, d, nrhs=1, p0=0, count=None, compute_mult=1):
         """Batched d_kkt_solve_new_rhs_res_mpc_hard_tv on the factor ipm() / ipm_solo() left in ws (at least one
@@ -285,8 +264,9 @@ class BatchSolver:
         (nprob, nrhs, N+1, 16) device tensors (b in state order, q in variable order [r | q]) or None for the
         problem's own rows; d: (nprob, nrhs, N+1, 32).  Returns ux, pi, lam, t with a leading (nprob, nrhs) shape --
         the tensors of kkt_buffers(nrhs), overwritten by the next call.  ws and the problem data are not written.
+        A tensor that is not on the solver's device is refused with ValueError before the library is called.
         Asynchronous on torch's current stream."""
-        count = self.nprob - p0 if count is None else count
+        p0, count = self._range(p0, count)
         out = self.kkt_buffers(nrhs)
         check(kkt_sets_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, nrhs, self.BAbt,
                             self.RSQrq, None, b, q, d, out, self.ws, compute_mult, self._stream()),
@@ -299,8 +279,9 @@ class BatchSolver:
         ipm_solo() left.  db, dq: (nprob, ndir, N+1, 16), dd: (nprob, ndir, N+1, 32), or None for a zero direction.
         Returns dux, dpi, dlam, dt with a leading (nprob, ndir) shape: the tensors of ``out`` (default: those of
         kkt_buffers(ndir), which the next kkt_new_rhs / kkt_tangent call of that set count overwrites).  ws and the
-        problem data are not written.  Asynchronous on torch's current stream."""
-        count = self.nprob - p0 if count is None else count
+        problem data are not written.  A direction that is not on the solver's device is refused with ValueError
+        before the library is called.  Asynchronous on torch's current stream."""
+        p0, count = self._range(p0, count)
         out = self.kkt_buffers(ndir) if out is None else out
         check(kkt_tangent_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, ndir,
                                self.BAbt, self.RSQrq, None, db, dq, dd, out, self.ws, compute_mult, self._stream()),
@@ -314,8 +295,9 @@ class BatchSolver:
         qbar, dbar), the gradients with respect to b, q and d, with a leading (nprob, nadj) shape: the pi, ux and lam
         tensors of ``out`` (default: those of kkt_buffers(nadj), which the next kkt_new_rhs / kkt_tangent /
         kkt_adjoint call of that set count overwrites).  want_b=False skips the multiplier half of the solve and
-        returns bbar as None.  ws and the problem data are not written.  Asynchronous on torch's current stream."""
-        count = self.nprob - p0 if count is None else count
+        returns bbar as None.  ws and the problem data are not written.  A cotangent that is not on the solver's device
+        is refused with ValueError before the library is called.  Asynchronous on torch's current stream."""
+        p0, count = self._range(p0, count)
         out = self.kkt_buffers(nadj) if out is None else out
         check(kkt_adjoint_call(self.torch, self.plan, C.byref(self.layout), self.N, self.nprob, p0, count, nadj,
                                self.BAbt, self.RSQrq, None, gux, gpi, glam, gt, out, self.ws, want_b, self._stream()),

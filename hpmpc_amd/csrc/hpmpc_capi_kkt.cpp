@@ -21,6 +21,17 @@ extern "C" long long hpmpc_mi355x_kkt_scratch_doubles(const hpmpc_mi355x_plan* P
 
 namespace {
 
+constexpr bool ocp_is_vector(int i) {
+    return i == OCP_b || i == OCP_q || i == OCP_r || i == OCP_lb || i == OCP_ub || i == OCP_lg || i == OCP_ug;
+}
+
+// A call on an OCP plan without one: true, g_err set with the message `who`.
+bool no_plan(const void* O, const char* who) {
+    if (O) return false;
+    hk_set_error(HPMPC_MI355X_EUNSUPPORTED, who);
+    return true;
+}
+
 // The checks and the argument blocks these calls share.  arrays: the caller's own required arrays are all there.
 // False: nothing to launch, g_err holds the call's return (an error, or 0 for a range without a problem).
 bool sets_args(KArgs& a, KktArgs& x, const hpmpc_mi355x_plan* plan, const hpmpc_mi355x_layout* lay, int nprob, int p0,
@@ -80,10 +91,7 @@ extern "C" int hpmpc_mi355x_ocp_kkt_batch(const hpmpc_mi355x_ocp_plan* O, int np
                                           const double* BAbt, const double* RSQrq, const double* DCt, const double* d,
                                           double* ux, double* pi, double* lam, double* t, const double* ws,
                                           double* scratch, void* stream) {
-    if (!O) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_kkt_batch: plan");
-        return g_err;
-    }
+    if (no_plan(O, "hpmpc_mi355x_ocp_kkt_batch: plan")) return g_err;
     return hpmpc_mi355x_kkt_new_rhs_batch(O->tile.get(), nullptr, nprob, p0, count, 1, BAbt, RSQrq, DCt, nullptr,
                                           nullptr, d, ux, pi, lam, t, ws, scratch, 1, stream);
 }
@@ -111,10 +119,7 @@ extern "C" int hpmpc_mi355x_ocp_tangent_batch(const hpmpc_mi355x_ocp_plan* O, co
                                               const double* RSQrq, const double* DCt, double* du, double* dx,
                                               double* dpi, double* dlam, double* dt, const double* ws, double* scratch,
                                               int compute_mult, void* stream) {
-    if (!O) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_tangent_batch: plan");
-        return g_err;
-    }
+    if (no_plan(O, "hpmpc_mi355x_ocp_tangent_batch: plan")) return g_err;
     KArgs a;
     TanArgs x;
     memset(&x, 0, sizeof x);
@@ -124,8 +129,7 @@ extern "C" int hpmpc_mi355x_ocp_tangent_batch(const hpmpc_mi355x_ocp_plan* O, co
                    "hpmpc_mi355x tangent call: ndir"))
         return g_err;
     for (int i = 0; i < OCP_NARR; i++) {
-        const bool vec = i == OCP_b || i == OCP_q || i == OCP_r || i == OCP_lb || i == OCP_ub || i == OCP_lg ||
-                         i == OCP_ug;
+        const bool vec = ocp_is_vector(i);
         if (!vec && dirs->ptr[i]) {
             hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_tangent_batch: matrix directions (A, B, Q, S, R, "
                                                     "C, D) are not supported");
@@ -168,37 +172,6 @@ extern "C" int hpmpc_mi355x_kkt_adjoint_batch(const hpmpc_mi355x_plan* plan, con
 }
 
 namespace {
-
-constexpr bool ocp_is_vector(int i) {
-    return i == OCP_b || i == OCP_q || i == OCP_r || i == OCP_lb || i == OCP_ub || i == OCP_lg || i == OCP_ug;
-}
-
-// The checks and argument blocks of the dense adjoint launch, shared by hpmpc_mi355x_ocp_adjoint_batch and
-// hpmpc_mi355x_ocp_adjoint_data_batch.  want: the vector gradients (a matrix entry is not looked at); any: the call has
-// an output; mult: the multiplier half of the solve runs.  False as for sets_args.
-bool ocp_adjoint_args(KArgs& a, AdjArgs& x, const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nadj,
-                      const double* BAbt, const double* RSQrq, const double* DCt, const double* const cot[5],
-                      const OcpGrad& want, bool any, bool mult, const double* ws, double* scratch, const char* who) {
-    memset(&x, 0, sizeof x);
-    if (!sets_args(a, x.k, O->tile.get(), nullptr, nprob, p0, count, nadj, BAbt, RSQrq, DCt, ws, scratch, any, mult,
-                   who, "hpmpc_mi355x adjoint call: nadj"))
-        return false;
-    const long long scot[5] = {O->su, O->sx, O->sp, O->sl, O->sl};
-    for (int i = 0; i < 5; i++) {
-        if (scot[i] > 0) {  // a cotangent the plan has no element of is never read
-            x.cot[i].p = cot[i];
-            x.cot[i].s = scot[i];
-        }
-    }
-    for (int i = 0; i < OCP_NARR; i++) {
-        if (ocp_is_vector(i) && O->dense[i] > 0) {
-            x.grad.p[i] = want.p[i];
-            x.grad.s[i] = want.s[i];
-        }
-    }
-    x.ost = O->d_st.get();
-    return true;
-}
 
 // The matrix entries of `grads` and the arrays they need -> m.  bbar / qbar / dbar and their strides are the caller's
 // to set.  False: refused, g_err set.
@@ -245,10 +218,61 @@ bool wants_matrix(const hpmpc_mi355x_ocp_grads* g) {
     return false;
 }
 
-bool no_plan(const void* O, const char* who) {
-    if (O) return false;
-    hk_set_error(HPMPC_MI355X_EUNSUPPORTED, who);
-    return true;
+// hpmpc_mi355x_ocp_adjoint_batch and hpmpc_mi355x_ocp_adjoint_data_batch: the dense adjoint launch for the vector
+// entries of `grads` and, when it has a matrix entry, the matrix gradients on the adjoint solution in the scratch, from
+// the base iterate ux, pi, lam (not read otherwise, so they may be null).  The checks run range, arrays, stride, and
+// every check of the second launch comes before the first.
+int ocp_adjoint(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int nadj, const double* BAbt,
+                const double* RSQrq, const double* DCt, const double* ux, const double* pi, const double* lam,
+                const double* const cot[5], const hpmpc_mi355x_ocp_grads* grads, const double* ws, double* scratch,
+                void* stream, const char* who) {
+    KArgs a;
+    AdjArgs x;
+    memset(&x, 0, sizeof x);
+    // any: the call has an output; mult: the multiplier half of the solve runs
+    bool any = false, mult = false, bad_stride = false;
+    for (int i = 0; grads && i < OCP_NARR; i++) {
+        if (!grads->ptr[i]) continue;
+        any = true;
+        mult = mult || ((i == OCP_b || i == OCP_A || i == OCP_B) && O->dense[i] > 0);
+        if (!ocp_is_vector(i)) continue;
+        bad_stride = bad_stride || grads->stride[i] < O->dense[i];
+        if (O->dense[i] > 0) {  // a vector the plan has no element of is never written
+            x.grad.p[i] = grads->ptr[i];
+            x.grad.s[i] = grads->stride[i];
+        }
+    }
+    if (!sets_args(a, x.k, O->tile.get(), nullptr, nprob, p0, count, nadj, BAbt, RSQrq, DCt, ws, scratch, any, mult,
+                   who, "hpmpc_mi355x adjoint call: nadj"))
+        return g_err;
+    if (bad_stride) {  // only the data call brings strides of its own
+        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_adjoint_data_batch: a stride below the array's size");
+        return g_err;
+    }
+    const long long scot[5] = {O->su, O->sx, O->sp, O->sl, O->sl};
+    for (int i = 0; i < 5; i++) {
+        if (scot[i] > 0) {  // a cotangent the plan has no element of is never read
+            x.cot[i].p = cot[i];
+            x.cot[i].s = scot[i];
+        }
+    }
+    x.ost = O->d_st.get();
+    MatGradArgs m;
+    const bool mats = wants_matrix(grads);
+    if (mats) {
+        if (!matgrad_args(m, O, nprob, p0, count, nadj, ux, pi, lam, grads, who)) return g_err;
+        const KktSet c = carve_set(scratch, O->N);  // where hk_kkt_adj leaves the dense call's qbar, bbar, dbar
+        m.qbar = c.dux;
+        m.bbar = m.pi ? c.dpi : nullptr;
+        m.dbar = m.lam ? c.res_d : nullptr;
+        m.sq = m.sb = m.sd = x.k.sS;
+    }
+    if (const int e = hk_kkt_adj_launch(&a, &x, count, (hipStream_t)stream))
+        return launch_error(e, "hk_kkt_adj launch failed");
+    if (mats)
+        if (const int e = hk_ocp_matgrad_launch(&m, (hipStream_t)stream))
+            return launch_error(e, "hk_ocp_matgrad launch failed");
+    return g_err = 0;
 }
 
 }  // namespace
@@ -260,27 +284,19 @@ extern "C" int hpmpc_mi355x_ocp_adjoint_batch(const hpmpc_mi355x_ocp_plan* O, in
                                               double* glb, double* gub, double* glg, double* gug, const double* ws,
                                               double* scratch, void* stream) {
     if (no_plan(O, "hpmpc_mi355x_ocp_adjoint_batch: plan")) return g_err;
-    KArgs a;
-    AdjArgs x;
     const double* cot[5] = {gu, gx, gpi, glam, gt};
-    OcpGrad want;
-    memset(&want, 0, sizeof want);
     const struct {
         int i;
         double* p;
-    } grads[] = {{OCP_b, gb}, {OCP_q, gq}, {OCP_r, gr}, {OCP_lb, glb}, {OCP_ub, gub}, {OCP_lg, glg}, {OCP_ug, gug}};
-    bool any = false;
-    for (const auto& g : grads) {
-        want.p[g.i] = g.p;
-        want.s[g.i] = O->dense[g.i];
-        any = any || g.p;
+    } vec[] = {{OCP_b, gb}, {OCP_q, gq}, {OCP_r, gr}, {OCP_lb, glb}, {OCP_ub, gub}, {OCP_lg, glg}, {OCP_ug, gug}};
+    hpmpc_mi355x_ocp_grads grads;
+    memset(&grads, 0, sizeof grads);
+    for (const auto& v : vec) {
+        grads.ptr[v.i] = v.p;
+        grads.stride[v.i] = O->dense[v.i];
     }
-    if (!ocp_adjoint_args(a, x, O, nprob, p0, count, nadj, BAbt, RSQrq, DCt, cot, want, any, gb && O->dense[OCP_b] > 0,
-                          ws, scratch, "hpmpc_mi355x_ocp_adjoint_batch"))
-        return g_err;
-    if (const int e = hk_kkt_adj_launch(&a, &x, count, (hipStream_t)stream))
-        return launch_error(e, "hk_kkt_adj launch failed");
-    return g_err = 0;
+    return ocp_adjoint(O, nprob, p0, count, nadj, BAbt, RSQrq, DCt, nullptr, nullptr, nullptr, cot, &grads, ws, scratch,
+                       stream, "hpmpc_mi355x_ocp_adjoint_batch");
 }
 
 extern "C" int hpmpc_mi355x_ocp_matrix_grads_batch(const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count,
@@ -321,47 +337,8 @@ extern "C" int hpmpc_mi355x_ocp_adjoint_data_batch(const hpmpc_mi355x_ocp_plan* 
                                                    const double* gpi, const double* glam, const double* gt,
                                                    const hpmpc_mi355x_ocp_grads* grads, const double* ws,
                                                    double* scratch, void* stream) {
-    const char* who = "hpmpc_mi355x_ocp_adjoint_data_batch";
     if (no_plan(O, "hpmpc_mi355x_ocp_adjoint_data_batch: plan")) return g_err;
-    KArgs a;
-    AdjArgs x;
     const double* cot[5] = {gu, gx, gpi, glam, gt};
-    OcpGrad want;
-    memset(&want, 0, sizeof want);
-    bool any = false, mult = false, bad_stride = false;
-    if (grads) {
-        for (int i = 0; i < OCP_NARR; i++) {
-            any = any || grads->ptr[i];
-            if (!grads->ptr[i]) continue;
-            if (ocp_is_vector(i)) {
-                want.p[i] = grads->ptr[i];
-                want.s[i] = grads->stride[i];
-                bad_stride = bad_stride || grads->stride[i] < O->dense[i];
-            }
-            mult = mult || ((i == OCP_b || i == OCP_A || i == OCP_B) && O->dense[i] > 0);
-        }
-    }
-    if (!ocp_adjoint_args(a, x, O, nprob, p0, count, nadj, BAbt, RSQrq, DCt, cot, want, any, mult, ws, scratch, who))
-        return g_err;
-    if (bad_stride) {
-        hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x_ocp_adjoint_data_batch: a stride below the array's size");
-        return g_err;
-    }
-    // every check of the second launch comes before the first
-    MatGradArgs m;
-    const bool mats = grads && wants_matrix(grads);
-    if (mats) {
-        if (!matgrad_args(m, O, nprob, p0, count, nadj, ux, pi, lam, grads, who)) return g_err;
-        const KktSet c = carve_set(scratch, O->N);  // where hk_kkt_adj leaves the dense call's qbar, bbar, dbar
-        m.qbar = c.dux;
-        m.bbar = m.pi ? c.dpi : nullptr;
-        m.dbar = m.lam ? c.res_d : nullptr;
-        m.sq = m.sb = m.sd = x.k.sS;
-    }
-    if (const int e = hk_kkt_adj_launch(&a, &x, count, (hipStream_t)stream))
-        return launch_error(e, "hk_kkt_adj launch failed");
-    if (mats)
-        if (const int e = hk_ocp_matgrad_launch(&m, (hipStream_t)stream))
-            return launch_error(e, "hk_ocp_matgrad launch failed");
-    return g_err = 0;
+    return ocp_adjoint(O, nprob, p0, count, nadj, BAbt, RSQrq, DCt, ux, pi, lam, cot, grads, ws, scratch, stream,
+                       "hpmpc_mi355x_ocp_adjoint_data_batch");
 }

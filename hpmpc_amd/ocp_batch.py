@@ -23,6 +23,7 @@ import ctypes as C
 import numpy as np
 
 from .bindings import check, lib, plan_args
+from .device import DeviceSolver
 
 KEYS = ("A", "B", "b", "Q", "S", "R", "q", "r", "lb", "ub", "C", "D", "lg", "ug")  # HkOcpArray / hpmpc_mi355x_ocp_data
 OUT_KEYS = ("u", "x", "pi", "lam", "t")
@@ -104,6 +105,13 @@ def unflatten_problems(flat, N, nx, nu, nb, ng, order="C", keys=None) -> list:
             P[key] = blocks
         out.append(P)
     return out
+
+
+def flatten_sets(sets, nsets, keys, order="C") -> dict:
+    """flatten_problems for ``nsets`` sets per problem: ``sets[p][r]`` is set r of problem p in the interface form ->
+    {key: (nprob, nsets, size) float64}."""
+    flat = flatten_problems([S for per in sets for S in per[:nsets]], order, keys)
+    return {key: v.reshape(len(sets), nsets, -1) for key, v in flat.items()}
 
 
 def kkt_set_arrays(problems):
@@ -228,25 +236,23 @@ def ocp_plan_create(N, nx, nu, nb, idxb, ng, order="C"):
     return (plan or None), L.hpmpc_mi355x_last_error(), keep
 
 
-class OcpBatchSolver:
+class OcpBatchSolver(DeviceSolver):
     """``nprob`` OCPs with the given stage sizes: owns the lib4 arrays, the iterate, the workspaces and the outputs
     (torch tensors on ``device``).  pack() -> solve() -> finish(), then any number of resolve() -> finish() or
     kkt_sets() / tangent() / adjoint() / adjoint_data() on the factor solve() left, all asynchronous on torch's current
     stream.
     There is no CPU fallback: without a GPU or the built library the constructor raises."""
 
-    def __init__(self, N, nx, nu, nb, idxb, ng, nprob, order="C", device="cuda", k_max=50):
-        import torch
+    _destroy = "hpmpc_mi355x_ocp_plan_destroy"
 
+    def __init__(self, N, nx, nu, nb, idxb, ng, nprob, order="C", device="cuda", k_max=50):
         if order not in ("C", "F"):
             raise ValueError("order is 'C' (row-major blocks) or 'F' (column-major blocks)")
-        if not torch.cuda.is_available():
-            raise RuntimeError("OcpBatchSolver needs a GPU (HIP device); there is no CPU fallback")
-        self.torch = torch
+        super().__init__(device)
+        torch = self.torch
         self.N, self.nprob, self.k_max, self.order = int(N), int(nprob), int(k_max), order
         self.nx, self.nu = [int(v) for v in nx], [int(v) for v in nu][:N] + [0]
         self.nb, self.ng = [int(v) for v in nb], [int(v) for v in ng]
-        self.dev = torch.device(device)
         L = lib()
         self.plan, err, self._keep = ocp_plan_create(N, self.nx, self.nu, self.nb, idxb, self.ng, order)
         if not self.plan:
@@ -272,30 +278,12 @@ class OcpBatchSolver:
         self.ret = torch.zeros(P, dtype=torch.int32, device=self.dev)
         self.stat = new(5 * max(self.k_max, 1))
 
-    def __del__(self):
-        try:
-            if getattr(self, "plan", None):
-                lib().hpmpc_mi355x_ocp_plan_destroy(self.plan)
-        except Exception:
-            pass
-
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.dev).cuda_stream
-
-    def _range(self, p0, count):
-        return p0, (self.nprob - p0 if count is None else count)
-
     def _vec(self, x, n, what):
-        """(pointer, problem stride) of a float64 device tensor: (nprob, n), or (n,) shared by every problem."""
-        torch = self.torch
-        if x.dtype != torch.float64 or x.device.type != self.dev.type:
-            raise ValueError(f"{what}: float64 tensor on {self.dev} expected")
-        if x.dim() == 1 and x.shape[0] == n and (n == 0 or x.stride(0) == 1):
-            return x.data_ptr(), 0
-        if x.dim() == 2 and tuple(x.shape) == (self.nprob, n) and (n == 0 or x.stride(1) == 1):
-            return x.data_ptr(), x.stride(0)
-        raise ValueError(f"{what}: shape ({self.nprob}, {n}) or ({n},) with unit inner stride expected, got "
-                         f"{tuple(x.shape)}")
+        """(pointer, problem stride) of a float64 device tensor: (nprob, n) with unit inner stride (the rows may be
+        apart), or (n,) shared by every problem (stride 0)."""
+        if x.dim() == 2 and x.shape[0] == self.nprob:
+            return self._tensor(x[0], (n,), what), x.stride(0)  # the first row's pointer is the tensor's
+        return self._tensor(x, (n,), what), 0
 
     def _ocp_data(self, data, one):
         """hpmpc_mi355x_ocp_data of {key: tensor}: ``one(key, x, n)`` gives (pointer, stride) of a given array of
@@ -317,11 +305,13 @@ class OcpBatchSolver:
         arrays = self.BAbt, self.RSQrq, self.DCt if self.sizes["DCt"] else None
         return tuple(None if x is None else x.data_ptr() for x in arrays) if ptr else arrays
 
+    def _out_sizes(self):
+        s = self.sizes
+        return dict(u=s["u"], x=s["x"], pi=s["pi_out"], lam=s["lam_out"], t=s["lam_out"])
+
     def _sized(self, o):
         """The tensors u, x, pi, lam, t of ``o``, allocated with at least one element, cut to their sizes."""
-        s = self.sizes
-        return dict(u=o["u"][..., :s["u"]], x=o["x"][..., :s["x"]], pi=o["pi"][..., :s["pi_out"]],
-                    lam=o["lam"][..., :s["lam_out"]], t=o["t"][..., :s["lam_out"]])
+        return {key: o[key][..., :n] for key, n in self._out_sizes().items()}
 
     def pack(self, data, matrices=True, warm=None, p0=0, count=None):
         """Dense device tensors -> BAbt, RSQrq, DCt, d (hk_ocp_pack).  ``data``: {key: tensor (nprob, size), or
@@ -353,13 +343,13 @@ class OcpBatchSolver:
         resolve() uses the scratch of nrhs = 1."""
         from .batch import kkt_buffers
 
-        if nrhs < 1:
-            raise ValueError("nrhs >= 1 expected")
-        bufs = self.__dict__.setdefault("_kkt", {})
-        if nrhs not in bufs:
-            bufs[nrhs] = kkt_buffers(self.torch, self.dev, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), self.N,
-                                     self.nprob, nrhs)
-        return bufs[nrhs]
+        return self._per_set("kkt", nrhs, lambda n: kkt_buffers(
+            self.torch, self.dev, lib().hpmpc_mi355x_ocp_tile_plan(self.plan), self.N, self.nprob, n))
+
+    def _dense_sets(self, kind, nsets, sizes):
+        """The cached dict {key: zeros (nprob, nsets, max(size, 1))} over ``sizes`` = {key: size}."""
+        return self._per_set(kind, nsets, lambda n: {key: self.torch.zeros(
+            (self.nprob, n, max(size, 1)), dtype=self.torch.float64, device=self.dev) for key, size in sizes.items()})
 
     def resolve(self, data, p0=0, count=None):
         """The batched c_order_ / fortran_order_d_solve_kkt_new_rhs_ocp_hard_tv: re-solve the last Newton system of
@@ -402,15 +392,7 @@ class OcpBatchSolver:
     def set_buffers(self, nsets: int = 1) -> dict:
         """The dense per-set tensors u, x, pi, lam, t of shape (nprob, nsets, max(size, 1)) that tangent(ndir=nsets)
         and kkt_sets(nrhs=nsets, dense=True) write (allocated on first use, then reused and overwritten)."""
-        if nsets < 1:
-            raise ValueError("at least one set per problem expected")
-        bufs = self.__dict__.setdefault("_sets", {})
-        if nsets not in bufs:
-            s = self.sizes
-            new = lambda n: self.torch.zeros((self.nprob, nsets, max(n, 1)), dtype=self.torch.float64, device=self.dev)
-            bufs[nsets] = dict(u=new(s["u"]), x=new(s["x"]), pi=new(s["pi_out"]), lam=new(s["lam_out"]),
-                               t=new(s["lam_out"]))
-        return bufs[nsets]
+        return self._dense_sets("sets", nsets, self._out_sizes())
 
     def tangent(self, dirs, ndir, p0=0, count=None, compute_mult=1):
         """Forward sensitivities of the re-solved plan (hpmpc_mi355x_ocp_tangent_batch): the directional derivative
@@ -421,17 +403,10 @@ class OcpBatchSolver:
         u, x, pi, lam, t of (nprob, ndir, size) tensors (du, dx, dpi, compact dlam, dt) -- those of
         set_buffers(ndir).  The equality-box fix of finish() is not applied to tangents.  compute_mult=0: pi comes
         back as zeros.  Neither ws nor the solver's data or iterate is written."""
-        torch = self.torch
         p0, count = self._range(p0, count)
-
-        def direction(key, x, n):
-            if x.dtype != torch.float64 or x.device.type != self.dev.type or not x.is_contiguous() or \
-                    (key in VEC_KEYS and tuple(x.shape) != (self.nprob, ndir, n)):
-                raise ValueError(f"direction {key}: contiguous float64 tensor ({self.nprob}, {ndir}, {n}) on "
-                                 f"{self.dev} expected")
-            return x.data_ptr(), n
-
-        ds = self._ocp_data(dirs, direction)
+        # a matrix key's shape is not looked at: the library refuses the key itself
+        ds = self._ocp_data(dirs, lambda key, x, n: (self._tensor(
+            x, (self.nprob, ndir, n) if key in VEC_KEYS else x.shape, f"direction {key}"), n))
         o = self.set_buffers(ndir)
         check(lib().hpmpc_mi355x_ocp_tangent_batch(
             self.plan, C.byref(ds), self.nprob, p0, count, ndir, *self._lib4(), o["u"].data_ptr(), o["x"].data_ptr(),
@@ -480,26 +455,12 @@ class OcpBatchSolver:
     def grad_buffers(self, nadj: int = 1) -> dict:
         """The dense per-set gradient tensors b, q, r, lb, ub, lg, ug of shape (nprob, nadj, max(size, 1)) that
         adjoint(nadj=nadj) writes (allocated on first use, then reused and overwritten)."""
-        if nadj < 1:
-            raise ValueError("at least one set per problem expected")
-        bufs = self.__dict__.setdefault("_grads", {})
-        if nadj not in bufs:
-            new = lambda n: self.torch.zeros((self.nprob, nadj, max(n, 1)), dtype=self.torch.float64, device=self.dev)
-            bufs[nadj] = {key: new(self.sizes[key]) for key in VEC_KEYS}
-        return bufs[nadj]
+        return self._dense_sets("grads", nadj, {key: self.sizes[key] for key in VEC_KEYS})
 
     def _cot_ptrs(self, cot, nadj):
         """The pointers gu, gx, gpi, glam, gt of the dense cotangents ``cot`` (None: zero), after checking them."""
-        torch, s = self.torch, self.sizes
-        size = dict(u=s["u"], x=s["x"], pi=s["pi_out"], lam=s["lam_out"], t=s["lam_out"])
-        ptrs = []
-        for key in OUT_KEYS:
-            x = cot.get(key)
-            if x is not None and (x.dtype != torch.float64 or x.device.type != self.dev.type or not x.is_contiguous()
-                                  or tuple(x.shape) != (self.nprob, nadj, size[key])):
-                raise ValueError(f"cotangent {key}: contiguous float64 tensor ({self.nprob}, {nadj}, {size[key]}) on "
-                                 f"{self.dev} expected")
-            ptrs.append(None if x is None else x.data_ptr())
+        ptrs = [self._tensor(cot.get(key), (self.nprob, nadj, n), f"cotangent {key}", optional=True)
+                for key, n in self._out_sizes().items()]
         if any(key not in OUT_KEYS for key in cot):
             raise ValueError(f"cotangents are keyed by {OUT_KEYS}")
         return ptrs
@@ -544,13 +505,7 @@ class OcpBatchSolver:
         """The dense per-set gradient tensors A, B, Q, S, R, C, D of shape (nprob, nadj, max(size, 1)) that
         matrix_gradients(nadj=nadj) and adjoint_data(nadj=nadj) write (allocated on first use, then reused and
         overwritten)."""
-        if nadj < 1:
-            raise ValueError("at least one set per problem expected")
-        bufs = self.__dict__.setdefault("_mgrads", {})
-        if nadj not in bufs:
-            new = lambda n: self.torch.zeros((self.nprob, nadj, max(n, 1)), dtype=self.torch.float64, device=self.dev)
-            bufs[nadj] = {key: new(self.sizes[key]) for key in MAT_KEYS}
-        return bufs[nadj]
+        return self._dense_sets("matrix_grads", nadj, {key: self.sizes[key] for key in MAT_KEYS})
 
     def _grads_struct(self, bufs, want):
         """hpmpc_mi355x_ocp_grads over the tensors ``bufs`` (nprob, nadj, >= size): the keys of ``want``, else null."""
@@ -564,15 +519,8 @@ class OcpBatchSolver:
         without finish()'s equality-box fix), or ``base`` = dict(ux=, pi=, lam=) of (nprob, sizes[key]) tensors."""
         if base is None:
             return self.ux.data_ptr(), self.pi.data_ptr(), self.lam.data_ptr()
-        out = []
-        for key in ("ux", "pi", "lam"):
-            x = base[key]
-            if x.dtype != self.torch.float64 or x.device.type != self.dev.type or not x.is_contiguous() or \
-                    tuple(x.shape) != (self.nprob, self.sizes[key]):
-                raise ValueError(f"base {key}: contiguous float64 tensor ({self.nprob}, {self.sizes[key]}) on "
-                                 f"{self.dev} expected")
-            out.append(x.data_ptr())
-        return tuple(out)
+        return tuple(self._tensor(base[key], (self.nprob, self.sizes[key]), f"base {key}")
+                     for key in ("ux", "pi", "lam"))
 
     def matrix_gradients(self, bbar, qbar, dbar, nadj, want=MAT_KEYS, base=None, p0=0, count=None):
         """Gradients with respect to the matrices from an adjoint solution (hpmpc_mi355x_ocp_matrix_grads_batch, one
@@ -584,22 +532,17 @@ class OcpBatchSolver:
         system on the persisted factor, not the derivative of a fully converged solve (include/hpmpc_mi355x.h).
         Returns {key: (nprob, nadj, sizes[key])} over ``want`` -- tensors of matrix_grad_buffers(nadj); blocks in the
         solver's order ("C" row-major / "F" column-major).  No input is written."""
-        torch = self.torch
         p0, count = self._range(p0, count)
         if not want or any(key not in MAT_KEYS for key in want):
             raise ValueError(f"want: a non-empty subset of {MAT_KEYS} expected")
-        for name, x, w in (("bbar", bbar, 16), ("qbar", qbar, 16), ("dbar", dbar, 32)):
-            if x is None and name == "bbar" and "A" not in want and "B" not in want:
-                continue
-            if x is None or tuple(x.shape) != (self.nprob, nadj, self.N + 1, w) or x.dtype != torch.float64 or \
-                    x.device.type != self.dev.type or not x.is_contiguous():
-                raise ValueError(f"{name}: contiguous float64 tensor of shape {(self.nprob, nadj, self.N + 1, w)} "
-                                 "expected")
+        bars = [self._tensor(x, (self.nprob, nadj, self.N + 1, w), name, optional)
+                for name, x, w, optional in (("bbar", bbar, 16, "A" not in want and "B" not in want),
+                                             ("qbar", qbar, 16, False), ("dbar", dbar, 32, False))]
         g = self.matrix_grad_buffers(nadj)
         gs = self._grads_struct(g, want)
         check(lib().hpmpc_mi355x_ocp_matrix_grads_batch(
-            self.plan, self.nprob, p0, count, nadj, *self._base_ptrs(base), None if bbar is None else bbar.data_ptr(),
-            qbar.data_ptr(), dbar.data_ptr(), C.byref(gs), self._stream()), "hpmpc_mi355x_ocp_matrix_grads_batch")
+            self.plan, self.nprob, p0, count, nadj, *self._base_ptrs(base), *bars, C.byref(gs), self._stream()),
+            "hpmpc_mi355x_ocp_matrix_grads_batch")
         return {key: g[key][..., :self.sizes[key]] for key in MAT_KEYS if key in want}
 
     def adjoint_data(self, cot, nadj, want=KEYS, base=None, p0=0, count=None):

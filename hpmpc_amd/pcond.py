@@ -19,23 +19,22 @@ import ctypes as C
 
 import numpy as np
 
-from .bindings import lib, plan_args
+from .bindings import check, lib, plan_args
+from .device import DeviceSolver
 from .ocp import OCPQP
 
 
-class PcondSolver:
+class PcondSolver(DeviceSolver):
     """A batch of OCP QPs (shared sizes), condensed into N2 blocks and solved by the condensed Riccati."""
 
-    def __init__(self, qp: OCPQP, N2: int, device="cuda"):
-        import torch
+    _destroy = "hpmpc_mi355x_pcond_plan_destroy"
 
-        if not torch.cuda.is_available():
-            raise RuntimeError("PcondSolver needs a GPU (HIP device); there is no CPU fallback")
+    def __init__(self, qp: OCPQP, N2: int, device="cuda"):
+        super().__init__(device)
         assert qp.batch is not None, "PcondSolver takes a batched OCPQP"
-        self.torch = torch
+        torch = self.torch
         self.qp = qp
         self.N, self.N2, self.nprob = qp.N, N2, qp.batch
-        self.dev = torch.device(device)
         L = lib()
         N = qp.N
         (nx, nu, nb, ng), idxp, self._keep = plan_args(qp.idxb, qp.nx, qp.nu, qp.nb, qp.ng)
@@ -76,44 +75,31 @@ class PcondSolver:
         self.lam2, self.t2 = z(s[8]), z(s[8])
         self.ux, self.pi, self.lam, self.t = z(s[3]), z(s[4]), z(s[2]), z(s[2])
 
-    def __del__(self):
-        try:
-            if getattr(self, "plan", None):
-                lib().hpmpc_mi355x_pcond_plan_destroy(self.plan)
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
-
     @staticmethod
     def _p(t):
         return C.c_void_p(t.data_ptr())
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed (code {rc})")
-
     def condense(self, p0=0, count=None):
-        count = self.nprob - p0 if count is None else count
+        p0, count = self._range(p0, count)
         p = self._p
-        self._check(lib().hpmpc_mi355x_pcond_batch(self.plan, self.nprob, p0, count, p(self.BAbt), p(self.RSQrq),
-                                                     p(self.d), p(self.G), p(self.BAbt2), p(self.RSQrq2),
-                                                     p(self.DCt2), p(self.d2), self._stream()), "pcond")
+        check(lib().hpmpc_mi355x_pcond_batch(self.plan, self.nprob, p0, count, p(self.BAbt), p(self.RSQrq), p(self.d),
+                                             p(self.G), p(self.BAbt2), p(self.RSQrq2), p(self.DCt2), p(self.d2),
+                                             self._stream()), "hpmpc_mi355x_pcond_batch")
 
     def riccati(self, p0=0, count=None, compute_pi=1):
-        count = self.nprob - p0 if count is None else count
+        p0, count = self._range(p0, count)
         p = self._p
-        self._check(lib().hpmpc_mi355x_pcond_ric_sv_batch(self.plan, self.nprob, p0, count, p(self.BAbt2),
-                                                            p(self.RSQrq2), p(self.ws2), p(self.ux2), p(self.pi2),
-                                                            compute_pi, self._stream()), "condensed sv")
+        check(lib().hpmpc_mi355x_pcond_ric_sv_batch(self.plan, self.nprob, p0, count, p(self.BAbt2), p(self.RSQrq2),
+                                                    p(self.ws2), p(self.ux2), p(self.pi2), compute_pi, self._stream()),
+              "hpmpc_mi355x_pcond_ric_sv_batch")
 
     def expand(self, p0=0, count=None):
-        count = self.nprob - p0 if count is None else count
+        p0, count = self._range(p0, count)
         p = self._p
-        self._check(lib().hpmpc_mi355x_pexpand_batch(self.plan, self.nprob, p0, count, p(self.BAbt), p(self.RSQrq),
-                                                       p(self.ux2), p(self.pi2), p(self.lam2), p(self.t2), p(self.ux),
-                                                       p(self.pi), p(self.lam), p(self.t), self._stream()), "expand")
+        check(lib().hpmpc_mi355x_pexpand_batch(self.plan, self.nprob, p0, count, p(self.BAbt), p(self.RSQrq),
+                                               p(self.ux2), p(self.pi2), p(self.lam2), p(self.t2), p(self.ux),
+                                               p(self.pi), p(self.lam), p(self.t), self._stream()),
+              "hpmpc_mi355x_pexpand_batch")
 
     def solve(self):
         """condense -> condensed Riccati -> expand for the whole batch (asynchronous on the current stream)."""
@@ -148,13 +134,13 @@ class PcondSolver:
             self.ret2 = torch.zeros(P, dtype=torch.int32, device=self.dev)
             self.stat2 = torch.zeros((P, 5 * max(k_max, 1)), dtype=torch.float64, device=self.dev)
             self._kmax = k_max
-        count = self.nprob - p0 if count is None else count
+        p0, count = self._range(p0, count)
         p = self._p
-        self._check(L.hpmpc_mi355x_wide_ipm_batch(self.wplan, P, p0, count, p(self.BAbt2), p(self.RSQrq2),
-                                                  p(self.DCt2), p(self.d2), p(self.ux2), p(self.pi2), p(self.lam2),
-                                                  p(self.t2), p(self.work2), k_max, mu0, mu_tol, alpha_min, 0, 1,
-                                                  p(self.kk2), p(self.ret2), p(self.stat2), self._stream()),
-                    "condensed IPM")
+        check(L.hpmpc_mi355x_wide_ipm_batch(self.wplan, P, p0, count, p(self.BAbt2), p(self.RSQrq2), p(self.DCt2),
+                                            p(self.d2), p(self.ux2), p(self.pi2), p(self.lam2), p(self.t2),
+                                            p(self.work2), k_max, mu0, mu_tol, alpha_min, 0, 1, p(self.kk2),
+                                            p(self.ret2), p(self.stat2), self._stream()),
+              "hpmpc_mi355x_wide_ipm_batch")
 
     def cond_sizes(self):
         """Stage sizes of the condensed problem (lists of N2+1): nx, nu, nb, ng."""

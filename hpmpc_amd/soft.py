@@ -14,6 +14,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from .bindings import check, lib, plan_args
+from .device import DeviceSolver
 from .ocp import mass_spring_dynamics, pack_lib4_batch, rup
 
 
@@ -259,27 +260,25 @@ def soft_plan_create(sq: SoftQP):
     return (plan or None), int(L.hpmpc_mi355x_last_error())
 
 
-class SoftBatchSolver:
+class SoftBatchSolver(DeviceSolver):
     """Device-resident batch of soft-constrained QPs + hpmpc_mi355x_ipm_soft_batch: every iteration of every problem
     in one launch on torch's current stream (torch is plumbing: allocation and streams).  There is no CPU fallback.
 
     ``shared=True`` keeps one copy of the BAbt / RSQrq blocks of stages >= 1 for the whole batch (they must be equal
     in every problem) and stage 0 per problem, through hpmpc_mi355x_layout's shared flags."""
 
+    _destroy = "hpmpc_mi355x_soft_plan_destroy"
+
     def __init__(self, sqs, k_max: int = 50, device="cuda", shared: bool = False):
         import ctypes as C
 
-        import torch
-
         from .batch import _Layout
 
-        if not torch.cuda.is_available():
-            raise RuntimeError("SoftBatchSolver needs a GPU (HIP device); there is no CPU fallback")
-        self.torch = torch
+        super().__init__(device)
+        torch = self.torch
         self.sqs = list(sqs)
         self.template = t = self.sqs[0]
         self.N, self.nprob, self.k_max = t.N, len(self.sqs), int(k_max)
-        self.dev = torch.device(device)
         L = lib()
         pk = pack_soft_batch(self.sqs)
         self.plan, err = soft_plan_create(t)
@@ -323,13 +322,6 @@ class SoftBatchSolver:
         self.ret = torch.zeros(P, dtype=torch.int32, device=self.dev)
         self.stat = torch.zeros((P, 5 * max(self.k_max, 1)), dtype=f64, device=self.dev)
 
-    def __del__(self):
-        try:
-            if getattr(self, "plan", None):
-                lib().hpmpc_mi355x_soft_plan_destroy(self.plan)
-        except Exception:
-            pass
-
     def set_ux(self, ux0):
         """Warm-start iterate: ux0[p][k] holds at least nu + nx values of problem p, stage k."""
         h = np.zeros((self.nprob, self.N + 1, 16))
@@ -347,7 +339,7 @@ class SoftBatchSolver:
 
         k_max = self.k_max if k_max is None else int(k_max)
         assert 0 <= k_max <= self.k_max
-        count = self.nprob - p0 if count is None else count
+        p0, count = self._range(p0, count)
         # stat keeps the stride the call uses: 5 k_max per problem
         stat = self.stat if k_max == self.k_max else self.stat.view(-1)[:self.nprob * 5 * max(k_max, 1)]
         self._stat_kmax = k_max
@@ -356,7 +348,7 @@ class SoftBatchSolver:
             self.Z.data_ptr(), self.z.data_ptr(), self.d.data_ptr(), self.ux.data_ptr(), self.pi.data_ptr(),
             self.lam.data_ptr(), self.t.data_ptr(), self.ws.data_ptr(), k_max, mu0, mu_tol, alpha_min, warm_start,
             compute_mult, self.kk.data_ptr(), self.ret.data_ptr(), stat.data_ptr(),
-            self.torch.cuda.current_stream(self.dev).cuda_stream), "hpmpc_mi355x_ipm_soft_batch")
+            self._stream()), "hpmpc_mi355x_ipm_soft_batch")
 
     def results(self) -> list:
         """Synchronise and return the per-problem dicts of unpack_soft_solution."""

@@ -21,7 +21,7 @@ import numpy as np
 import test_gpu_kkt_batch as KB
 from helpers import TOL_IPM
 from hpmpc_amd.cabi import bq_from_qp
-from hpmpc_amd.ocp_batch import VEC_KEYS
+from hpmpc_amd.ocp_batch import VEC_KEYS, flatten_sets
 from ocp_batch_cases import IO, K_MAX, compact, problems
 
 CASES = ("V", "V0", "F", "S")
@@ -88,12 +88,7 @@ def dense_err(got, ref):
 
 def flat_dirs(deltas, ndir):
     """deltas[p][r] (interface-form deltas) -> {key: (nprob, ndir, size)} numpy arrays for OcpBatchSolver.tangent"""
-    out = {}
-    for key in VEC_KEYS:
-        rows = [[np.concatenate([np.asarray(v, dtype=np.float64).ravel() for v in D[key]] + [np.zeros(0)])
-                 for D in row] for row in deltas]
-        out[key] = np.array(rows, dtype=np.float64).reshape(len(deltas), ndir, -1)
-    return out
+    return flatten_sets(deltas, ndir, VEC_KEYS)
 
 
 class TanRefs:

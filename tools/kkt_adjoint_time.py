@@ -19,7 +19,6 @@ thermal drift hit them alike), `warmup` such rounds, then the median, minimum an
 GB/s against the bytes a set must move (its problem's BAbt, RSQrq, DCt and factor once, its vectors in and out;
 work-vector traffic not counted).  Prints one JSON line.
 """
-import argparse
 import os
 import sys
 
@@ -27,11 +26,11 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from batch_time import ARGS, CASE, NX, alternated, emit, tiled_batch  # noqa: E402
-from kkt_tangent_time import VEC_KEYS, tangent_bytes  # noqa: E402
+from batch_time import (NX, alternated, cotangent_tensors, cotangents, direction_tensors, emit, parser,  # noqa: E402
+                        rhs_sets, solved_batch)
+from kkt_tangent_time import tangent_bytes  # noqa: E402
 
 NSETS = (1, 8, 12)
-COT_KEYS = ("u", "x", "pi", "lam", "t")
 
 
 def adjoint_bytes(sv):
@@ -44,46 +43,17 @@ def adjoint_bytes(sv):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--nprob", type=int, default=1024)
-    ap.add_argument("--distinct", type=int, default=64)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--runs", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser().parse_args()
     import torch
 
-    import iface_oracle as IO
-    from hpmpc_amd.ocp_batch import adjoint_set_arrays, ocp_dense_layout, tangent_set_arrays, unflatten_problems
-
-    Ps, nd, sv, tile, data = tiled_batch(torch, a.nprob, a.distinct)
-    P0 = Ps[0]
-    sv.pack(data)
-    sv.solve(**ARGS)
-    torch.cuda.synchronize()
-    kk, ret = sv.kk.cpu().numpy(), sv.ret.cpu().numpy()
-    out = dict(case=CASE, nprob=a.nprob, distinct=nd, args=ARGS, runs=a.runs, warmup=a.warmup,
-               bytes_per_set=dict(tangent=tangent_bytes(sv), adjoint=adjoint_bytes(sv)),
-               solve=dict(kk_min=int(kk.min()), kk_max=int(kk.max()), ret_nonzero=int((ret != 0).sum())))
-    sizes = {k: P0[k] for k in ("N", "nx", "nu", "nb", "ng")}
-    shape = (P0["N"], P0["nx"], P0["nu"], P0["nb"], P0["ng"])
-    deltas = [[dict(sizes, **{key: [np.asarray(y) - np.asarray(x) for x, y in zip(P[key], IO.new_rhs(P, seed=6 + r)[key])]
-                              for key in VEC_KEYS}) for r in range(max(NSETS))] for P in Ps]
-    osz = ocp_dense_layout(*shape)["sizes"]
+    Ps, nd, sv, tile, out = solved_batch(torch, a,
+                                         lambda sv: dict(tangent=tangent_bytes(sv), adjoint=adjoint_bytes(sv)))
+    deltas = rhs_sets(Ps, max(NSETS))[1]
     rng = np.random.default_rng(7)
-    cots = {key: rng.standard_normal((nd, max(NSETS), osz[key])) for key in COT_KEYS}
+    cots = cotangents(rng, Ps, max(NSETS))
     for n in NSETS:
-        dev = lambda x: torch.from_numpy(tile(x.reshape((nd, n) + x.shape[1:]))).to(sv.dev)
-        db, dq, dd = (dev(x) for x in tangent_set_arrays([D for row in deltas for D in row[:n]]))
-        dirs = {}
-        for key in VEC_KEYS:
-            rows = np.array([[np.concatenate([np.ravel(v) for v in D[key]] + [np.zeros(0)]) for D in row[:n]]
-                             for row in deltas]).reshape(nd, n, -1)
-            dirs[key] = torch.from_numpy(tile(rows)).to(sv.dev)
-        cot = {key: torch.from_numpy(tile(np.ascontiguousarray(v[:, :n]))).to(sv.dev) for key, v in cots.items()}
-        per = unflatten_problems({key: v[:, :n].reshape(nd * n, -1) for key, v in cots.items()}, *shape,
-                                 keys=list(COT_KEYS))
-        gux, gpi, glam, gt = (dev(x) for x in adjoint_set_arrays([dict(sizes, **G) for G in per]))
+        (db, dq, dd), dirs = direction_tensors(torch, sv, tile, deltas, n)
+        cot, (gux, gpi, glam, gt) = cotangent_tensors(torch, sv, tile, Ps, cots, n)
         t = alternated(torch, dict(tangent=lambda: sv.tangent_sets(db, dq, dd, n),
                                    tangent_dense=lambda: sv.tangent(dirs, n),
                                    adjoint=lambda: sv.adjoint_sets(gux, gpi, glam, gt, n),

@@ -15,14 +15,13 @@ every right-hand-side set still has its own arrays in HBM).
                      not measured on the whole batch).
 Prints one JSON line.
 """
-import argparse
 import os
 import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from batch_time import ARGS, CASE, emit, tiled_batch, timed  # noqa: E402
+from batch_time import ARGS, CASE, emit, parser, rhs_sets, set_tensors, tiled_batch, timed  # noqa: E402
 
 NRHS = (1, 8)
 
@@ -55,17 +54,9 @@ def part1_loop(Ps, sets):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--nprob", type=int, default=1024)
-    ap.add_argument("--distinct", type=int, default=64)
-    ap.add_argument("--base", type=int, default=64)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--runs", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser(base=64).parse_args()
     import torch
 
-    import iface_oracle as IO
     from hpmpc_amd.ocp_batch import kkt_set_arrays
 
     Ps, nd, sv, tile, data = tiled_batch(torch, a.nprob, a.distinct)
@@ -76,11 +67,9 @@ def main():
     kk, ret = sv.kk.cpu().numpy(), sv.ret.cpu().numpy()
     out["solve"].update(kk_min=int(kk.min()), kk_max=int(kk.max()), kk_sum=int(kk.sum()),
                         ret_nonzero=int((ret != 0).sum()))
-    sets = [[IO.new_rhs(P, seed=6 + r) for r in range(max(NRHS))] for P in Ps]
+    sets = rhs_sets(Ps, max(NRHS))[0]
     for nrhs in NRHS:
-        b, q, d = kkt_set_arrays([S for row in sets for S in row[:nrhs]])
-        dev = lambda x: torch.from_numpy(tile(x.reshape((nd, nrhs) + x.shape[1:]))).to(sv.dev)
-        b, q, d = dev(b), dev(q), dev(d)
+        b, q, d = set_tensors(torch, sv, tile, kkt_set_arrays([S for row in sets for S in row[:nrhs]]), nrhs)
         t = timed(torch, lambda: sv.kkt_sets(b, q, d, nrhs=nrhs), a.warmup, a.runs)
         nsets = a.nprob * nrhs
         t.update(sets=nsets, us_per_set=t["ms"] * 1e3 / nsets, GBps=out["bytes_per_set"] * nsets / (t["ms"] * 1e-3) / 1e9,

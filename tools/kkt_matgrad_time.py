@@ -16,7 +16,6 @@ for matgrad GB/s against the bytes a set must move: per stage nx1 (nu + nx) + (n
 written and 128 read (the base iterate's 64 are shared by a problem's sets and counted once per set all the same).
 Prints one JSON line.
 """
-import argparse
 import os
 import sys
 
@@ -24,10 +23,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from batch_time import ARGS, CASE, alternated, emit, tiled_batch  # noqa: E402
+from batch_time import alternated, cotangent_tensors, cotangents, emit, parser, solved_batch  # noqa: E402
 
 NADJ = (1, 4)
-COT_KEYS = ("u", "x", "pi", "lam", "t")
 
 
 def matgrad_bytes(sv):
@@ -39,37 +37,15 @@ def matgrad_bytes(sv):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--nprob", type=int, default=1024)
-    ap.add_argument("--distinct", type=int, default=64)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--runs", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser().parse_args()
     import torch
 
-    from hpmpc_amd.ocp_batch import KEYS, MAT_KEYS, adjoint_set_arrays, ocp_dense_layout, unflatten_problems
+    from hpmpc_amd.ocp_batch import KEYS, MAT_KEYS
 
-    Ps, nd, sv, tile, data = tiled_batch(torch, a.nprob, a.distinct)
-    P0 = Ps[0]
-    sv.pack(data)
-    sv.solve(**ARGS)
-    torch.cuda.synchronize()
-    kk, ret = sv.kk.cpu().numpy(), sv.ret.cpu().numpy()
-    out = dict(case=CASE, nprob=a.nprob, distinct=nd, args=ARGS, runs=a.runs, warmup=a.warmup,
-               bytes_per_set=dict(matgrad=matgrad_bytes(sv)),
-               solve=dict(kk_min=int(kk.min()), kk_max=int(kk.max()), ret_nonzero=int((ret != 0).sum())))
-    sizes = {k: P0[k] for k in ("N", "nx", "nu", "nb", "ng")}
-    shape = (P0["N"], P0["nx"], P0["nu"], P0["nb"], P0["ng"])
-    osz = ocp_dense_layout(*shape)["sizes"]
-    rng = np.random.default_rng(7)
-    cots = {key: rng.standard_normal((nd, max(NADJ), osz[key])) for key in COT_KEYS}
+    Ps, nd, sv, tile, out = solved_batch(torch, a, lambda sv: dict(matgrad=matgrad_bytes(sv)))
+    cots = cotangents(np.random.default_rng(7), Ps, max(NADJ))
     for n in NADJ:
-        dev = lambda x: torch.from_numpy(tile(x.reshape((nd, n) + x.shape[1:]))).to(sv.dev)
-        cot = {key: torch.from_numpy(tile(np.ascontiguousarray(v[:, :n]))).to(sv.dev) for key, v in cots.items()}
-        per = unflatten_problems({key: v[:, :n].reshape(nd * n, -1) for key, v in cots.items()}, *shape,
-                                 keys=list(COT_KEYS))
-        gux, gpi, glam, gt = (dev(x) for x in adjoint_set_arrays([dict(sizes, **G) for G in per]))
+        cot, (gux, gpi, glam, gt) = cotangent_tensors(torch, sv, tile, Ps, cots, n)
         bbar, qbar, dbar = (x.clone() for x in sv.adjoint_sets(gux, gpi, glam, gt, n))
         t = alternated(torch, dict(adjoint_dense=lambda: sv.adjoint(cot, n),
                                    adjoint_data=lambda: sv.adjoint_data(cot, n),

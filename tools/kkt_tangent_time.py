@@ -17,19 +17,15 @@ and thermal drift hit them alike), `warmup` such rounds, then the median, minimu
 and GB/s against the bytes a set must move (its problem's BAbt, RSQrq and factor once, its vectors in and out;
 work-vector traffic not counted).  Prints one JSON line.
 """
-import argparse
 import os
 import sys
 
-import numpy as np
-
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from batch_time import ARGS, CASE, alternated, emit, tiled_batch  # noqa: E402
+from batch_time import alternated, direction_tensors, emit, parser, rhs_sets, set_tensors, solved_batch  # noqa: E402
 from kkt_batch_time import set_bytes  # noqa: E402
 
 NDIR = (1, 8, 12)
-VEC_KEYS = ("b", "q", "r", "lb", "ub", "lg", "ug")
 
 
 def tangent_bytes(sv):
@@ -42,40 +38,16 @@ def tangent_bytes(sv):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--nprob", type=int, default=1024)
-    ap.add_argument("--distinct", type=int, default=64)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--runs", type=int, default=10)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    a = parser().parse_args()
     import torch
 
-    import iface_oracle as IO
-    from hpmpc_amd.ocp_batch import kkt_set_arrays, tangent_set_arrays
+    from hpmpc_amd.ocp_batch import kkt_set_arrays
 
-    Ps, nd, sv, tile, data = tiled_batch(torch, a.nprob, a.distinct)
-    P0 = Ps[0]
-    sv.pack(data)
-    sv.solve(**ARGS)
-    torch.cuda.synchronize()
-    kk, ret = sv.kk.cpu().numpy(), sv.ret.cpu().numpy()
-    out = dict(case=CASE, nprob=a.nprob, distinct=nd,
-               args=ARGS, runs=a.runs, warmup=a.warmup, bytes_per_set=dict(resolve=set_bytes(sv), tangent=tangent_bytes(sv)),
-               solve=dict(kk_min=int(kk.min()), kk_max=int(kk.max()), ret_nonzero=int((ret != 0).sum())))
-    sets = [[IO.new_rhs(P, seed=6 + r) for r in range(max(NDIR))] for P in Ps]
-    sizes = {k: P0[k] for k in ("N", "nx", "nu", "nb", "ng")}
-    deltas = [[dict(sizes, **{key: [np.asarray(y) - np.asarray(x) for x, y in zip(P[key], S[key])] for key in VEC_KEYS})
-               for S in row] for P, row in zip(Ps, sets)]
+    Ps, nd, sv, tile, out = solved_batch(torch, a, lambda sv: dict(resolve=set_bytes(sv), tangent=tangent_bytes(sv)))
+    sets, deltas = rhs_sets(Ps, max(NDIR))
     for ndir in NDIR:
-        dev = lambda x: torch.from_numpy(tile(x.reshape((nd, ndir) + x.shape[1:]))).to(sv.dev)
-        b, q, d = (dev(x) for x in kkt_set_arrays([S for row in sets for S in row[:ndir]]))
-        db, dq, dd = (dev(x) for x in tangent_set_arrays([D for row in deltas for D in row[:ndir]]))
-        dirs = {}
-        for key in VEC_KEYS:
-            rows = np.array([[np.concatenate([np.ravel(v) for v in D[key]] + [np.zeros(0)]) for D in row[:ndir]]
-                             for row in deltas]).reshape(nd, ndir, -1)
-            dirs[key] = torch.from_numpy(tile(rows)).to(sv.dev)
+        b, q, d = set_tensors(torch, sv, tile, kkt_set_arrays([S for row in sets for S in row[:ndir]]), ndir)
+        (db, dq, dd), dirs = direction_tensors(torch, sv, tile, deltas, ndir)
         t = alternated(torch, dict(resolve=lambda: sv.kkt_sets(b, q, d, nrhs=ndir),
                                    resolve_dense=lambda: sv.kkt_sets(b, q, d, nrhs=ndir, dense=True),
                                    tangent=lambda: sv.tangent_sets(db, dq, dd, ndir),
