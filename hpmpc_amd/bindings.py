@@ -67,6 +67,8 @@ _SIG = dict(
     ocp_adjoint_batch="i:piiiipppppppppppppppppp",
     ocp_matrix_grads_batch="i:piiiipppppppp",
     ocp_adjoint_data_batch="i:piiiippppppppppppppp",
+    ocp_matrix_dirs_batch="i:ppiiiippppppp",
+    ocp_tangent_data_batch="i:ppiiiipppppppppppppip",
 )
 # {function name: (restype, argtypes)}
 SIGNATURES = {"hpmpc_mi355x_" + n: (_CTYPE[s[0]], [_CTYPE[c] for c in s[2:]]) for n, s in _SIG.items()}

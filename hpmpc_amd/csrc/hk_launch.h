@@ -14,6 +14,7 @@ struct WideIpmArgs;
 struct TanArgs;
 struct AdjArgs;
 struct MatGradArgs;
+struct MatDirArgs;
 struct OcpPackArgs;
 struct OcpUnpackArgs;
 
@@ -33,10 +34,14 @@ int hk_soft_ipm_launch(const KArgs* a, const SoftArgs* s, int count, hipStream_t
 int hk_kkt_rhs_launch(const KArgs* a, const KktArgs* x, int count, hipStream_t stream);
 // hk_tan.hip: the batched KKT tangent solve, x->k.nrhs direction sets for each of `count` problems in one launch
 int hk_kkt_tan_launch(const KArgs* a, const TanArgs* x, int count, hipStream_t stream);
+// the same in dense mode with the prologue skipped: the sets' scratch blocks already hold the seed rows (hk_ocp_matdir)
+int hk_kkt_tan_seeded_launch(const KArgs* a, const TanArgs* x, int count, hipStream_t stream);
 // hk_adj.hip: the batched KKT adjoint solve, x->k.nrhs cotangent sets for each of `count` problems in one launch
 int hk_kkt_adj_launch(const KArgs* a, const AdjArgs* x, int count, hipStream_t stream);
 // hk_matgrad.hip: the OCP matrix gradients, one workgroup per (stage, set) of a->count * a->nadj sets in one launch
 int hk_ocp_matgrad_launch(const MatGradArgs* a, hipStream_t stream);
+// hk_matdir.hip: the OCP matrix directions, one workgroup per (stage, set) of a->count * a->ndir sets in one launch
+int hk_ocp_matdir_launch(const MatDirArgs* a, hipStream_t stream);
 // hk_wide.hip (which: HkWideLaunch; args: the WideArgs / PcArgs / PxArgs of that kernel) and hk_wide_ipm.hip
 int hk_wide_launch(int which, const void* args, int count, int lds_doubles, hipStream_t stream);
 int hk_wide_ipm_launch(const WideIpmArgs* a, int count, int lds_doubles, hipStream_t stream);

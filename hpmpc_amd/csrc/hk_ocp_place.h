@@ -1,7 +1,8 @@
 // hk_ocp_place.h -- where the OCP front end's dense vectors sit in the solver's padded stage vectors, and back: one
 // definition of each placement for hk_ocp_pack, hk_ocp_pack_vectors, hk_ocp_unpack (hk_ocp.hip) and the dense prologue
 // and epilogue of hk_kkt_tan (hk_tan.hip), the transposes of both for those of hk_kkt_adj (hk_adj.hip), and the slots
-// hk_ocp_matgrad (hk_matgrad.hip) reads by dense index.  Device code only; lane l of a wavefront owns one element.
+// hk_ocp_matgrad (hk_matgrad.hip) and hk_ocp_matdir (hk_matdir.hip) read by dense index.  Device code only; lane l of a
+// wavefront owns one element.
 //
 // In: stage k's seed row, 64 doubles -- lanes 0..15 b_k (state order), 16..31 [r_k | q_k] (variable order), 32..63 d_k =
 // [lb pnb | ub pnb | lg png | ug png]; and the warm start ux_k = [u0_k | x0_k | 0 ..].
@@ -158,11 +159,25 @@ __device__ __forceinline__ void ocp_grad_store(const OcpStage& s, const OcpGrads
     }
 }
 
-// ---- by dense index (hk_ocp_matgrad, hk_matgrad.hip): the slot of input j / state j in the V16 stage vector in
+// ---- by dense index (hk_ocp_matgrad, hk_matgrad.hip; hk_ocp_matdir, hk_matdir.hip): the slot of input j / state j in the V16 stage vector in
 // variable order [u | x], and of general constraint l's lower / upper side in the V32 stage vector ----
 __device__ __forceinline__ int ocp_slot_u(const OcpStage&, int j) { return j; }
 __device__ __forceinline__ int ocp_slot_x(const OcpStage& s, int j) { return s.nu + j; }
 __device__ __forceinline__ int ocp_slot_lg(const OcpStage& s, int l) { return 2 * s.pnb + l; }
 __device__ __forceinline__ int ocp_slot_ug(const OcpStage& s, int l) { return 2 * s.pnb + s.png + l; }
+// and back (hk_ocp_matdir, hk_matdir.hip, whose lane l owns slot l of the seed row): the input / state of slot v of the
+// V16 vector in variable order, the general constraint of slot c of the V32 vector's lower / upper side; -1: none
+__device__ __forceinline__ int ocp_u_of_slot(const OcpStage& s, int v) { return v >= 0 && v < s.nu ? v : -1; }
+__device__ __forceinline__ int ocp_x_of_slot(const OcpStage& s, int v) {
+    return v >= s.nu && v < s.nu + s.nx ? v - s.nu : -1;
+}
+__device__ __forceinline__ int ocp_lg_of_slot(const OcpStage& s, int c) {
+    const int g = c - 2 * s.pnb;
+    return g >= 0 && g < s.ng ? g : -1;
+}
+__device__ __forceinline__ int ocp_ug_of_slot(const OcpStage& s, int c) {
+    const int g = c - 2 * s.pnb - s.png;
+    return g >= 0 && g < s.ng ? g : -1;
+}
 
 }  // namespace

@@ -28,7 +28,9 @@ constexpr int TAN_CH = 4;
 
 }  // namespace
 
-template <class FX>
+// SEEDED (dense mode only; hpmpc_mi355x_ocp_tangent_data_batch): res_b / res_q / res_d of the scratch already hold the
+// seed rows -- hk_ocp_matdir (hk_matdir.hip) wrote them earlier on the stream -- and the prologue is skipped.
+template <class FX, bool SEEDED = false>
 __global__ __launch_bounds__(64) void hk_kkt_tan(KArgs a, TanArgs x) {
     const LdsTabs T = lds_tables(a);
     Scratch& sm = *T.sm;
@@ -55,7 +57,7 @@ __global__ __launch_bounds__(64) void hk_kkt_tan(KArgs a, TanArgs x) {
         // every element of the three vectors is written, zero where the direction is null or the slot is padding
         const auto in = [&](int i) -> const double* { return x.in[i].p ? x.in[i].p + s * x.in[i].s : nullptr; };
         const OcpVecs dir{in(OCP_b), in(OCP_q), in(OCP_r), in(OCP_lb), in(OCP_ub), in(OCP_lg), in(OCP_ug)};
-        for (int k0 = 0; k0 <= N; k0 += TAN_CH) {
+        for (int k0 = 0; !SEEDED && k0 <= N; k0 += TAN_CH) {
             long long bits[TAN_CH];
 #pragma unroll
             for (int j = 0; j < TAN_CH; j++) {
@@ -123,4 +125,10 @@ __global__ __launch_bounds__(64) void hk_kkt_tan(KArgs a, TanArgs x) {
 extern "C" int hk_kkt_tan_launch(const KArgs* a, const TanArgs* x, int count, hipStream_t stream) {
     return kkt_sets_launch(a, x, count, x->k.nrhs, stream,
                            [](auto fx) { return &hk_kkt_tan<typename decltype(fx)::type>; });
+}
+
+extern "C" int hk_kkt_tan_seeded_launch(const KArgs* a, const TanArgs* x, int count, hipStream_t stream) {
+    if (!x->ost) return -1;  // the padded front end reads its directions in place: nothing to seed
+    return kkt_sets_launch(a, x, count, x->k.nrhs, stream,
+                           [](auto fx) { return &hk_kkt_tan<typename decltype(fx)::type, true>; });
 }

@@ -6,11 +6,14 @@
 // an OCP plan), ndir direction sets per problem (hk_kkt_tan, hk_tan.hip); and that tangent's transpose, the KKT adjoint
 // solve hpmpc_mi355x_kkt_adjoint_batch / hpmpc_mi355x_ocp_adjoint_batch, nadj cotangent sets per problem (hk_kkt_adj,
 // hk_adj.hip), and on its solution the gradients with respect to the dense matrices,
-// hpmpc_mi355x_ocp_matrix_grads_batch / hpmpc_mi355x_ocp_adjoint_data_batch (hk_ocp_matgrad, hk_matgrad.hip).  The
+// hpmpc_mi355x_ocp_matrix_grads_batch / hpmpc_mi355x_ocp_adjoint_data_batch (hk_ocp_matgrad, hk_matgrad.hip), and
+// forward the seed rows of directions in all fourteen dense arrays, hpmpc_mi355x_ocp_matrix_dirs_batch, and the tangent
+// solve on them, hpmpc_mi355x_ocp_tangent_data_batch (hk_ocp_matdir, hk_matdir.hip, then hk_kkt_tan).  The
 // workspaces an IPM left (hpmpc_mi355x_ipm_batch, _ipm_solo, _ocp_ipm_batch) are read only; each set's work vectors
 // live in the caller's scratch (kkt_scratch_doubles, hk_kkt_args.h).  The core calls carry a DCt array, so they take
 // tile plans with general constraints (batch_args with DCT_ARRAY).
 #include "hk_adj_args.h"
+#include "hk_matdir_args.h"
 #include "hk_matgrad_args.h"
 #include "hk_ocp_plan.h"
 #include "hk_tan_args.h"
@@ -327,6 +330,104 @@ extern "C" int hpmpc_mi355x_ocp_matrix_grads_batch(const hpmpc_mi355x_ocp_plan* 
     m.sd = m.sV32;
     if (const int e = hk_ocp_matgrad_launch(&m, (hipStream_t)stream))
         return launch_error(e, "hk_ocp_matgrad launch failed");
+    return g_err = 0;
+}
+
+namespace {
+
+// The fourteen entries of `dirs` and the base iterate they need -> m.  db / dq / dd and their strides are the caller's
+// to set.  False: refused, g_err set.
+bool matdir_args(MatDirArgs& m, const hpmpc_mi355x_ocp_plan* O, int nprob, int p0, int count, int ndir,
+                 const double* ux, const double* pi, const double* lam, const hpmpc_mi355x_ocp_data* dirs,
+                 const char* who) {
+    memset(&m, 0, sizeof m);
+    bool ab = false, cd = false;
+    for (int i = 0; i < OCP_NARR; i++) {
+        if (!dirs->ptr[i]) continue;
+        if (dirs->stride[i] < O->dense[i]) {
+            hk_set_error(HPMPC_MI355X_EUNSUPPORTED, "hpmpc_mi355x matrix directions: a stride below the array's size");
+            return false;
+        }
+        if (O->dense[i] == 0) continue;  // an array the plan has no element of is never read
+        m.dir[i].p = dirs->ptr[i];
+        m.dir[i].s = dirs->stride[i];
+        ab = ab || i == OCP_A || i == OCP_B;
+        cd = cd || i == OCP_C || i == OCP_D;
+    }
+    if (!ux || (ab && !pi) || (cd && !lam)) {
+        null_array(who);
+        return false;
+    }
+    const long long n1 = O->N + 1;
+    m.N = O->N;
+    m.nprob = nprob;
+    m.p0 = p0;
+    m.count = count;
+    m.ndir = ndir;
+    m.row_major = O->row_major;
+    m.st = O->d_st.get();
+    m.ux = ux;
+    m.pi = ab ? pi : nullptr;
+    m.lam = cd ? lam : nullptr;
+    m.sV16 = n1 * V16;
+    m.sV32 = n1 * V32;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int hpmpc_mi355x_ocp_matrix_dirs_batch(const hpmpc_mi355x_ocp_plan* O, const hpmpc_mi355x_ocp_data* dirs,
+                                                  int nprob, int p0, int count, int ndir, const double* ux,
+                                                  const double* pi, const double* lam, double* db, double* dq,
+                                                  double* dd, void* stream) {
+    const char* who = "hpmpc_mi355x_ocp_matrix_dirs_batch";
+    if (no_plan(O, "hpmpc_mi355x_ocp_matrix_dirs_batch: plan")) return g_err;
+    g_err = 0;
+    if (!range_ok(O, nprob, p0, count, who) || !sets_ok(nprob, ndir, "hpmpc_mi355x tangent call: ndir") || count == 0)
+        return g_err;
+    if (!dirs || !db || !dq || !dd) return null_array(who);
+    MatDirArgs m;
+    if (!matdir_args(m, O, nprob, p0, count, ndir, ux, pi, lam, dirs, who)) return g_err;
+    m.db = db;
+    m.dq = dq;
+    m.dd = dd;
+    m.sb = m.sq = m.sV16;
+    m.sd = m.sV32;
+    if (const int e = hk_ocp_matdir_launch(&m, (hipStream_t)stream))
+        return launch_error(e, "hk_ocp_matdir launch failed");
+    return g_err = 0;
+}
+
+// The seed launch into res_b / res_q / res_d of each set's scratch block, then hk_kkt_tan with its dense prologue
+// skipped.  The checks run range, arrays, stride, and every check of the second launch comes before the first.
+extern "C" int hpmpc_mi355x_ocp_tangent_data_batch(const hpmpc_mi355x_ocp_plan* O, const hpmpc_mi355x_ocp_data* dirs,
+                                                   int nprob, int p0, int count, int ndir, const double* BAbt,
+                                                   const double* RSQrq, const double* DCt, const double* ux,
+                                                   const double* pi, const double* lam, double* du, double* dx,
+                                                   double* dpi, double* dlam, double* dt, const double* ws,
+                                                   double* scratch, int compute_mult, void* stream) {
+    const char* who = "hpmpc_mi355x_ocp_tangent_data_batch";
+    if (no_plan(O, "hpmpc_mi355x_ocp_tangent_data_batch: plan")) return g_err;
+    KArgs a;
+    TanArgs x;
+    memset(&x, 0, sizeof x);
+    const OcpOut out = ocp_out(O, du, dx, dpi, dlam, dt);
+    if (!sets_args(a, x.k, O->tile.get(), nullptr, nprob, p0, count, ndir, BAbt, RSQrq, DCt, ws, scratch,
+                   dirs && ocp_out_ok(out, true), compute_mult, who, "hpmpc_mi355x tangent call: ndir"))
+        return g_err;
+    MatDirArgs m;
+    if (!matdir_args(m, O, nprob, p0, count, ndir, ux, pi, lam, dirs, who)) return g_err;
+    const KktSet c = carve_set(scratch, O->N);  // where hk_kkt_tan's dense prologue leaves the seed rows
+    m.db = c.res_b;
+    m.dq = c.res_q;
+    m.dd = c.res_d;
+    m.sb = m.sq = m.sd = x.k.sS;
+    x.ost = O->d_st.get();
+    x.out = out;
+    if (const int e = hk_ocp_matdir_launch(&m, (hipStream_t)stream))
+        return launch_error(e, "hk_ocp_matdir launch failed");
+    if (const int e = hk_kkt_tan_seeded_launch(&a, &x, count, (hipStream_t)stream))
+        return launch_error(e, "hk_kkt_tan launch failed");
     return g_err = 0;
 }
 

@@ -1,7 +1,8 @@
 """The batched OCP solve as a differentiable torch layer: ``ocp_solve(solver, data)`` runs OcpBatchSolver's pack ->
 solve -> finish and its backward is one OcpBatchSolver.adjoint_data call (hpmpc_mi355x_ocp_adjoint_data_batch: the KKT
-adjoint solve hk_kkt_adj, then the matrix gradients hk_ocp_matgrad).  torch is plumbing here; both directions are HIP
-kernels and there is no CPU fallback.
+adjoint solve hk_kkt_adj, then the matrix gradients hk_ocp_matgrad); under torch.autograd.forward_ad its jvp is one
+OcpBatchSolver.tangent_data call (hpmpc_mi355x_ocp_tangent_data_batch: the matrix directions hk_ocp_matdir, then the
+KKT tangent solve hk_kkt_tan).  torch is plumbing here; every direction is a HIP kernel and there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -47,6 +48,20 @@ def _function():
                         grads[i] = got[key][:, 0].sum(0) if shared else got[key][:, 0].clone()
             return (None, None, None, None, None, *grads)
 
+        @staticmethod
+        def jvp(ctx, *tins):
+            sv = ctx.solver
+            if getattr(sv, "_autograd_token", None) is not ctx.token:
+                raise RuntimeError("ocp_solve: the solver ran another ocp_solve since this forward; its factor and "
+                                   "iterate are gone")
+            dirs = {}
+            for key, t, shared in zip(ctx.keys, tins[5:], ctx.shared):
+                if t is not None:  # a shared tensor's tangent moves every problem's array
+                    t = t.detach()
+                    dirs[key] = (t.expand(sv.nprob, -1) if shared else t).reshape(sv.nprob, 1, -1).contiguous()
+            got = sv.tangent_data(dirs, 1)
+            return tuple(got[key][:, 0].clone() for key in OUT_KEYS)  # the buffers are the solver's
+
     _OcpSolve = OcpSolve
     return OcpSolve
 
@@ -66,8 +81,14 @@ def ocp_solve(solver, data, mu0=2.0, mu_tol=1e-10, alpha_min=1e-8):
     receive None.  Q and R receive the gradient for symmetric perturbations; the blocks of a time-invariant matrix are
     separate inputs here and their gradients are not summed over the stages.
 
-    What is differentiated: the linearised KKT system on the factor solve() persisted -- the exact transpose of the
-    re-solve's tangent in the vectors and of the matrix tangent defined in include/hpmpc_mi355x.h -- at the raw iterate,
+    Forward mode (torch.autograd.forward_ad): the tangents of the five outputs are one solver.tangent_data(..., 1) on
+    the tangents of the inputs that have one -- a shared (size,) tensor's tangent is expanded over the problems, an
+    input without a tangent does not move; Q and R act through the symmetric parts of their tangents.  One solve gives
+    the derivative of the whole plan along one parameter direction, where backward takes one per output element.
+
+    What is differentiated, in both modes: the linearised KKT system on the factor solve() persisted -- the re-solve's
+    tangent in the vectors and the matrix tangent defined in include/hpmpc_mi355x.h (forward), and their exact
+    transposes (backward) -- at the raw iterate,
     without finish()'s equality-box fix.  That factor belongs to the last Newton system of the IPM, formed one iterate
     before the returned point, so this is not the derivative of a fully converged solve: finite differences of whole
     solves agree to about 1e-3 relative, and torch.autograd.gradcheck is the wrong test for it.  Problems with

@@ -142,7 +142,7 @@ def kkt_set_arrays(problems):
 
 
 VEC_KEYS = ("b", "q", "r", "lb", "ub", "lg", "ug")  # the dense arrays a tangent direction may have
-MAT_KEYS = ("A", "B", "Q", "S", "R", "C", "D")  # the others: gradients only (matrix_gradients, adjoint_data)
+MAT_KEYS = ("A", "B", "Q", "S", "R", "C", "D")  # the others: matrix_gradients / adjoint_data, matrix_directions / tangent_data
 
 
 def tangent_set_arrays(problem_deltas):
@@ -239,8 +239,8 @@ def ocp_plan_create(N, nx, nu, nb, idxb, ng, order="C"):
 class OcpBatchSolver(DeviceSolver):
     """``nprob`` OCPs with the given stage sizes: owns the lib4 arrays, the iterate, the workspaces and the outputs
     (torch tensors on ``device``).  pack() -> solve() -> finish(), then any number of resolve() -> finish() or
-    kkt_sets() / tangent() / adjoint() / adjoint_data() on the factor solve() left, all asynchronous on torch's current
-    stream.
+    kkt_sets() / tangent() / tangent_data() / adjoint() / adjoint_data() on the factor solve() left, all asynchronous on
+    torch's current stream.
     There is no CPU fallback: without a GPU or the built library the constructor raises."""
 
     _destroy = "hpmpc_mi355x_ocp_plan_destroy"
@@ -399,7 +399,7 @@ class OcpBatchSolver(DeviceSolver):
         of what resolve() computes with respect to its b, q, r and bounds, ``ndir`` directions per problem in one
         launch on the factor of solve().  ``dirs``: {key: contiguous float64 device tensor (nprob, ndir,
         sizes[key])} for any of b, q, r, lb, ub, lg, ug; a missing (or None) key is a zero direction.  A matrix key
-        is passed on and refused by the library: directions in A, B, Q, S, R, C, D are out of scope.  Returns the dict
+        is passed on and refused by the library: directions in A, B, Q, S, R, C, D are tangent_data()'s.  Returns the dict
         u, x, pi, lam, t of (nprob, ndir, size) tensors (du, dx, dpi, compact dlam, dt) -- those of
         set_buffers(ndir).  The equality-box fix of finish() is not applied to tangents.  compute_mult=0: pi comes
         back as zeros.  Neither ws nor the solver's data or iterate is written."""
@@ -565,6 +565,55 @@ class OcpBatchSolver(DeviceSolver):
             self.ws.data_ptr(), self.kkt_buffers(nadj)["scratch"].data_ptr(), self._stream()),
             "hpmpc_mi355x_ocp_adjoint_data_batch")
         return {key: g[key][..., :self.sizes[key]] for key in KEYS if key in want}
+
+    def direction_buffers(self, ndir: int = 1) -> dict:
+        """The padded per-set seed rows db, dq (nprob, ndir, N+1, 16) and dd (nprob, ndir, N+1, 32) that
+        matrix_directions(ndir=ndir) writes (allocated on first use, then reused and overwritten).  They are not the
+        kkt_buffers tensors, so tangent_sets() may read them while it writes its own."""
+        zeros = lambda n, w: self.torch.zeros((self.nprob, n, self.N + 1, w), dtype=self.torch.float64, device=self.dev)
+        return self._per_set("dirs", ndir, lambda n: dict(db=zeros(n, 16), dq=zeros(n, 16), dd=zeros(n, 32)))
+
+    def _dirs_struct(self, dirs, ndir):
+        """hpmpc_mi355x_ocp_data of the direction tensors {key: (nprob, ndir, sizes[key])} over any of the fourteen
+        arrays (strides between sets); a missing (or None) key is null."""
+        if any(key not in KEYS for key in dirs):
+            raise ValueError(f"directions are keyed by {KEYS}")
+        return self._ocp_data(dirs, lambda key, x, n: (self._tensor(x, (self.nprob, ndir, n), f"direction {key}"), n))
+
+    def matrix_directions(self, dirs, ndir, base=None, p0=0, count=None):
+        """The seed rows of directions in any of the fourteen data arrays (hpmpc_mi355x_ocp_matrix_dirs_batch, one
+        launch): per stage db = db + dA x + dB u, dr = dr + sym(dR) u + dS x + dB' pi + dD' w, dq = dq + sym(dQ) x +
+        dS' u + dA' pi + dC' w, dd_lg / dd_ug = dlg / dug - (dC x + dD u), with w = lam_ug - lam_lg and sym(M) =
+        (M + M') / 2, at the base iterate (``base``, default the solver's own ux, pi, lam; as for matrix_gradients).
+        ``dirs``: {key: contiguous float64 device tensor (nprob, ndir, sizes[key])}, blocks in the solver's order; a
+        missing (or None) vector key is a zero direction, a missing matrix key contributes nothing.  Returns (db, dq,
+        dd), the tensors of direction_buffers(ndir), in the layouts tangent_sets() takes.  No input is written."""
+        p0, count = self._range(p0, count)
+        ds = self._dirs_struct(dirs, ndir)
+        o = self.direction_buffers(ndir)
+        check(lib().hpmpc_mi355x_ocp_matrix_dirs_batch(
+            self.plan, C.byref(ds), self.nprob, p0, count, ndir, *self._base_ptrs(base), o["db"].data_ptr(),
+            o["dq"].data_ptr(), o["dd"].data_ptr(), self._stream()), "hpmpc_mi355x_ocp_matrix_dirs_batch")
+        return o["db"], o["dq"], o["dd"]
+
+    def tangent_data(self, dirs, ndir, base=None, p0=0, count=None, compute_mult=1):
+        """Forward sensitivities with respect to any of the fourteen data arrays (hpmpc_mi355x_ocp_tangent_data_batch):
+        matrix_directions()'s launch into the sets' scratch, then tangent()'s solve on those seed rows, on one stream
+        with nothing in between -- one Riccati solve per direction set gives the derivative of the whole plan.  ``dirs``
+        and ``base`` as for matrix_directions().  Returns the dict u, x, pi, lam, t of (nprob, ndir, size) tensors --
+        those of set_buffers(ndir); without matrix keys bit for bit tangent()'s.  This is the linearised KKT system on
+        the persisted factor -- the forward twin of adjoint_data(): sum(g * tangent_data(d)) == sum(adjoint_data(g) * d)
+        up to rounding, Q and R acting through their symmetric parts -- not the derivative of a fully converged solve
+        (include/hpmpc_mi355x.h).  Neither ws nor the solver's data or iterate is written."""
+        p0, count = self._range(p0, count)
+        ds = self._dirs_struct(dirs, ndir)
+        o = self.set_buffers(ndir)
+        check(lib().hpmpc_mi355x_ocp_tangent_data_batch(
+            self.plan, C.byref(ds), self.nprob, p0, count, ndir, *self._lib4(), *self._base_ptrs(base),
+            o["u"].data_ptr(), o["x"].data_ptr(), o["pi"].data_ptr(), o["lam"].data_ptr(), o["t"].data_ptr(),
+            self.ws.data_ptr(), self.kkt_buffers(ndir)["scratch"].data_ptr(), compute_mult, self._stream()),
+            "hpmpc_mi355x_ocp_tangent_data_batch")
+        return self._sized(o)
 
     def x0_gradient(self, A0, S0, grads):
         """The chain rule of x0_directions: the gradient with respect to an x_0 folded into stage 0 (b_0 = A_0 x_0 + b,

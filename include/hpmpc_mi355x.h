@@ -633,8 +633,9 @@ int hpmpc_mi355x_ocp_unpack_sets(const hpmpc_mi355x_ocp_plan *plan, int nprob, i
  * problems [p0, p0+count) are read or written; count = 0 returns 0.  ndir < 1, a bad range, a null required pointer,
  * a null DCt with ng > 0 or a refused launch return HPMPC_MI355X_EUNSUPPORTED and write nothing.
  * Reverse mode is the adjoint solve below, and the gradients with respect to the matrices follow it
- * (hpmpc_mi355x_ocp_matrix_grads_batch).  Out of scope, refused or absent rather than half-built: DIRECTIONS in the
- * matrices (A, B, Q, S, R, C, D) for this forward call, and per-set residual norms. */
+ * (hpmpc_mi355x_ocp_matrix_grads_batch).  Directions in the matrices (A, B, Q, S, R, C, D) are a seed launch in front
+ * of this solve: hpmpc_mi355x_ocp_matrix_dirs_batch / hpmpc_mi355x_ocp_tangent_data_batch at the end of this header.
+ * Out of scope, absent rather than half-built: per-set residual norms. */
 int hpmpc_mi355x_kkt_tangent_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi355x_layout *lay, int nprob, int p0,
                                    int count, int ndir, const double *BAbt, const double *RSQrq, const double *DCt,
                                    const double *db, const double *dq, const double *dd, double *dux, double *dpi,
@@ -643,7 +644,7 @@ int hpmpc_mi355x_kkt_tangent_batch(const hpmpc_mi355x_plan *plan, const hpmpc_mi
 /* The same for dense directions and dense results on an OCP plan (packed default layout).  dirs: only the vector
  * entries b, q, r, lb, ub, lg, ug are read; stride[i] is the number of doubles between consecutive SETS (nprob * ndir
  * of them, problem-major), a null pointer is a zero direction, and a non-null matrix entry (A, B, Q, S, R, C, D) is
- * refused with HPMPC_MI355X_EUNSUPPORTED.  Results per set: du shaped like r, dx like q, dpi like b, dlam / dt compact
+ * refused with HPMPC_MI355X_EUNSUPPORTED (hpmpc_mi355x_ocp_tangent_data_batch takes them).  Results per set: du shaped like r, dx like q, dpi like b, dlam / dt compact
  * as [lb nb | ub nb | lg ng | ug ng]; all (nprob, ndir, size) with the per-problem sizes of hpmpc_mi355x_ocp_sizes
  * [23..26].  The equality-box fix of hpmpc_mi355x_ocp_finish_batch is NOT applied to tangents: the fix overwrites
  * u with the bound where lb == ub, a property of the base point; the tangent of such an input is what the Newton
@@ -755,6 +756,54 @@ int hpmpc_mi355x_ocp_adjoint_data_batch(const hpmpc_mi355x_ocp_plan *plan, int n
                                         const double *gpi, const double *glam, const double *gt,
                                         const hpmpc_mi355x_ocp_grads *grads, const double *ws, double *scratch,
                                         void *stream);
+
+/* ---- directions in all fourteen data arrays: the matrix tangent T_M, forward ----
+ * The forward evaluation of the map whose transpose the matrix gradients above are.  At a fixed base iterate z = (ux, pi,
+ * lam), ux_k = [u_k | x_k], a direction dtheta in the data moves the residuals of the KKT system by the SEED ROW, per
+ * stage k,
+ *   db_k    = db + dA_k x_k + dB_k u_k
+ *   dr_k    = dr + sym(dR_k) u_k + dS_k x_k + dB_k' pi_k + dD_k' w_k
+ *   dq_k    = dq + sym(dQ_k) x_k + dS_k' u_k + dA_k' pi_k + dC_k' w_k
+ *   dd_lg,k = dlg - (dC_k x_k + dD_k u_k),   dd_ug,k = dug - (dC_k x_k + dD_k u_k),   dd_lb = dlb,   dd_ub = dub
+ * with w_k = lam_ug,k - lam_lg,k, and the tangent is T_M(dtheta) = T(db, [dr | dq], dd) with T the tangent map of
+ * hpmpc_mi355x_kkt_tangent_batch.  Conventions: pi_k is the multiplier of stage k's dynamics and has nx[k+1] entries;
+ * stage N has no A, B, R, S, D block; sym(M) = (M + M') / 2, so dQ and dR need not be symmetric -- only their
+ * symmetric parts act, as the kernels read only the lower triangle of RSQrq -- and <gQ, dQ>, <gR, dR> pair exactly with
+ * the symmetric-perturbation gradients of hpmpc_mi355x_ocp_matrix_grads_batch for ANY dQ, dR: <g, T_M(dtheta)> =
+ * <G, dtheta> over all fourteen arrays, up to rounding.  Blocks of a time-invariant matrix are separate entries: the
+ * caller repeats its direction over the stages.
+ * What the quantity is: the linearised KKT system on the persisted factor, the exact forward twin of the matrix
+ * gradients.  It is NOT the derivative of a fully converged solve: the factor belongs to the last Newton system of the
+ * IPM, which was formed one iterate before the returned point (the figures of the matrix gradients' paragraph apply).
+ * Exactly linear in the direction: directions scaled by a power of two give the scaled result bit for bit.
+ * dirs: an hpmpc_mi355x_ocp_data whose stride[i] counts the doubles between consecutive SETS (nprob * ndir of them,
+ * problem-major), at least the array's per-problem size.  All fourteen entries are read and any may be null: a null
+ * vector entry is a zero direction, a null matrix entry contributes no term (not an added zero, so with every matrix
+ * entry null the row is the vector directions' bit for bit).  Each element's terms are summed in one fixed order: the
+ * vector direction first, then the products in the order of the formulas above from left to right, within a matrix by
+ * rising index; a set's row does not depend on the other sets of the call. */
+/* The core: one launch (hk_ocp_matdir), one workgroup per (stage, set).  ux, pi, lam: the base iterate per problem in
+ * the solver's padded layouts (16, 16, 32 doubles per stage) -- the IPM's, or a re-solve's.  db, dq, dd: the seed rows,
+ * padded per-set arrays (16 / 16 / 32 doubles per stage, nprob * ndir sets), directly usable as the db, dq, dd of
+ * hpmpc_mi355x_kkt_tangent_batch; every element of the sets in range is written, padding as zeros, nothing else is,
+ * and no input is written.  ux is required; pi when an A or B direction is given; lam when the plan has ng > 0 and a
+ * C or D direction is given.  Asynchronous on `stream`; only the sets of problems [p0, p0+count) are read or written;
+ * count = 0 returns 0.  ndir < 1, a bad range, a null plan, a null required pointer, a stride below the array's
+ * per-problem size for a given entry or a refused launch return HPMPC_MI355X_EUNSUPPORTED and write nothing. */
+int hpmpc_mi355x_ocp_matrix_dirs_batch(const hpmpc_mi355x_ocp_plan *plan, const hpmpc_mi355x_ocp_data *dirs, int nprob,
+                                       int p0, int count, int ndir, const double *ux, const double *pi,
+                                       const double *lam, double *db, double *dq, double *dd, void *stream);
+/* The tangent for directions in any of the fourteen arrays in one call: the seed launch above into each set's scratch
+ * block, then the launch of hpmpc_mi355x_ocp_tangent_batch on the same stream with its seeding skipped and its
+ * unpacking unchanged: no padded array of the caller's, no host synchronisation.  Results du, dx, dpi, dlam, dt, and
+ * BAbt, RSQrq, DCt, ws, scratch (hpmpc_mi355x_kkt_scratch_doubles per set) and compute_mult as for that call; ux, pi,
+ * lam as above.  With every matrix entry null the results are bit for bit those of hpmpc_mi355x_ocp_tangent_batch.
+ * Every check of both launches comes before the first; refusals as above and as the tangent call's. */
+int hpmpc_mi355x_ocp_tangent_data_batch(const hpmpc_mi355x_ocp_plan *plan, const hpmpc_mi355x_ocp_data *dirs, int nprob,
+                                        int p0, int count, int ndir, const double *BAbt, const double *RSQrq,
+                                        const double *DCt, const double *ux, const double *pi, const double *lam,
+                                        double *du, double *dx, double *dpi, double *dlam, double *dt, const double *ws,
+                                        double *scratch, int compute_mult, void *stream);
 
 #ifdef __cplusplus
 }
