@@ -14,6 +14,10 @@ Preconditions (`usable`):
   3. every used problem has max |dbar_ref| >= 1e-2 over lb, ub, lg, ug (the constraint half is exercised).
 Gate of a comparison against the reference (the GATES rule): max(TOL_IPM, 4 x the two builds' spread on that problem
 and cotangent), relative to max(1, |ref|).  No gate comes from the product's output.
+
+Measured at the wide cases H, E, B (all ten seeds used; 220 / 276 / 180 columns per problem): worst build spread of
+the reference adjoint H 1.2e-11, E 1.7e-12, B 5.4e-13; max |dbar_ref| >= 5.5 / 4.1 / 3.6 on every problem.  H leaves a
+factor of two under TOL_IPM / 4.
 """
 import numpy as np
 

@@ -12,10 +12,18 @@ off the diagonal.  No outer-product formula enters: the residuals are evaluated 
 Preconditions (`usable`):
   1. the problems used are exactly AdjRefs.usable(case) (which asserts its own three): at most 1 of 10 left out;
   2. the reference gradients of the two oracle builds differ by at most TOL_IPM / 4 on every used problem;
-  3. on case V every used problem has max |gC_ref| >= 1e-2 and max |gD_ref| >= 1e-2 (the constraint blocks are
-     exercised).
+  3. on every case with general constraints (ocp_batch_cases.GENERAL: V and E) every used problem has max |gC_ref| >=
+     1e-2 and max |gD_ref| >= 1e-2 (the constraint blocks are exercised).
 Gate of a comparison against the reference (the GATES rule): max(TOL_IPM, 4 x the two builds' spread on that
 problem), relative to max(1, |ref|).  No gate comes from the product's output.
+
+Cost.  The reference moves one matrix element at a time through the oracle's residual routine: 912 to 2416 elements
+per problem of the wide cases H, E, B, about 2 s per problem (1 to 3.5 s measured).  For those three cases (WIDE) the
+reference gradients are computed for the first N_WIDE = 3 seeds of AdjRefs.usable(case) and those three problems are
+compared -- the vector gradients that test_adjoint_data_matches_the_reference checks beside them too, which
+test_adjoint_matches_the_reference compares on all ten.  AdjRefs.usable itself still runs over all ten seeds, and
+that is where the 1-of-10 cap is asserted.  V, V0, F and S stay at ten.  Measured on those three seeds: worst build
+spread H 3.1e-13, E 6.5e-12, B 9.5e-15; on E max |gC_ref| >= 1.35 and max |gD_ref| >= 0.45.
 """
 import numpy as np
 
@@ -23,9 +31,10 @@ import kkt_adjoint_cases as AC
 from helpers import TOL_IPM
 from hpmpc_amd.cabi import bq_from_qp
 from hpmpc_amd.ocp_batch import MAT_KEYS, VEC_KEYS, flatten_problems
-from ocp_batch_cases import IO
+from ocp_batch_cases import GENERAL, IO
 
 CASES = AC.CASES
+WIDE, N_WIDE = ("H", "E", "B"), 3  # the cases whose reference gradients are computed for the first three seeds only
 CD_ACTIVE = 1e-2
 SYM_KEYS = ("Q", "R")
 
@@ -166,10 +175,15 @@ class MatRefs:
         """the GATES rule from the two builds' spread on one problem"""
         return max(TOL_IPM, 4 * mat_err(alt, ref))
 
+    def seeds(self, case):
+        """AdjRefs.usable(case) (asserted there over all ten seeds); of a WIDE case its first N_WIDE"""
+        seeds = self.adj.usable(case)
+        return seeds[:N_WIDE] if case in WIDE else seeds
+
     def measure(self, case):
         """Per usable seed: the two builds' spread on the reference gradients, their element count, max |gC|, |gD|."""
         rows = []
-        for seed in self.adj.usable(case):
+        for seed in self.seeds(case):
             ref, alt = self.gradients(case, seed)
             big = lambda key: float(max([np.max(np.abs(M), initial=0.0) for M in ref[key]] + [0.0]))
             rows.append(dict(seed=seed, spread=mat_err(alt, ref), nel=sum(M.size for key in MAT_KEYS for M in ref[key]),
@@ -180,12 +194,14 @@ class MatRefs:
         """The seeds of the case a test may use, with the three preconditions asserted."""
         key = ("usable", case)
         if key not in self.cache:
-            seeds = self.adj.usable(case)
+            full = self.adj.usable(case)
+            assert len(full) >= len(AC.TC.SEEDS) - 1, (case, full)
+            seeds = self.seeds(case)
             rows = self.measure(case)
-            assert [r["seed"] for r in rows] == seeds and len(seeds) >= len(AC.TC.SEEDS) - 1, (case, seeds)
+            assert [r["seed"] for r in rows] == seeds, (case, seeds)
             for r in rows:
                 assert r["spread"] <= TOL_IPM / 4, (case, r)
-                if case == "V":
+                if case in GENERAL:
                     assert r["gC"] >= CD_ACTIVE and r["gD"] >= CD_ACTIVE, (case, r)
             self.cache[key] = seeds
         return self.cache[key]

@@ -18,7 +18,16 @@ CASES = {
     "F": (4, [0, 8, 8, 8, 8], [3, 3, 3, 3], 3, 4, None),         # inner stages of the compiled (3, 8) class
     "S": (1, [2, 2], [1], 1, 1, None),                           # smallest horizon
     "R": (2, [2, 2, 2], [1, 1], 1, 0, None),                     # one box per stage: the shape of the refusal tests
+    # the compiled (4, 12) class on stages 1 to 3: nu + nx = 16, nb = 8 on every stage, an empty x_0
+    "H": (5, [0, 12, 12, 12, 12, 12], [4] * 5, 4, 4, None),
+    # the 16-wide tile edge with general constraints.  nb + ng slots per stage: 4 + 12 (a variable x_0 under general
+    # constraints), 8 + 8 (nb 5, ng 7: both padded), 8 + 8 with nu = 0 and nx = 16, 8 + 8 with every box on an input,
+    # and a last stage with nx = 16, nb = 0, ng = 16
+    "E": (4, [4, 12, 16, 8, 16], [4, 4, 0, 8], [4, 2, 0, 8, 0], [0, 3, 8, 0, 0], [12, 7, 8, 8, 16]),
+    # all boxes: stages 1 and 2 have nu = nx = 8 and nb = 16 (the 32 slots of lam / t full), stage 0 nx 4 and nb 12
+    "B": (3, [4, 8, 8, 8], [8, 8, 8], [8, 8, 8, 0], [4, 8, 8, 8], None),
 }
+GENERAL = tuple(c for c, v in CASES.items() if v[5] is not None and any(v[5]))  # cases with a non-zero ng entry
 ARGS = dict(mu0=2.0, mu_tol=1e-10, alpha_min=1e-8)
 K_MAX = 50
 
@@ -98,8 +107,9 @@ def oracle_ref(oracle, P, warm=None):
 
 def check(got, ref, keys=("u", "x", "pi", "lam", "t"), tag=""):
     """The gates of tests/test_gpu_iface.py: identical status and kk, the vectors at TOL_IPM relative to
-    max(1, |ref|), inf_norm_res at 1e-9 absolute."""
+    max(1, |ref|), inf_norm_res at 1e-9 absolute.  Returns the worst relative error of the vectors."""
     assert (got["status"], got["kk"]) == (ref["status"], ref["kk"]), tag
+    worst = 0.0
     for key in keys:
         assert len(got[key]) == len(ref[key]), (tag, key)
         for k, (g, r) in enumerate(zip(got[key], ref[key])):
@@ -108,7 +118,9 @@ def check(got, ref, keys=("u", "x", "pi", "lam", "t"), tag=""):
             if r.size:
                 e = float(np.max(np.abs(g - r) / np.maximum(1.0, np.abs(r))))
                 assert e <= TOL_IPM, (tag, key, k, e)
+                worst = max(worst, e)
     np.testing.assert_allclose(got["inf_norm_res"], ref["inf_norm_res"], rtol=0, atol=1e-9)
+    return worst
 
 
 def solve_batch(Ps, order, warm=None):

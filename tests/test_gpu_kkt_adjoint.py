@@ -132,7 +132,7 @@ def test_adjoint_matches_the_reference(refs, case, order):
 
 
 # ----------------------------------------------------------------------------- 2: exactly linear, no base leak
-@pytest.mark.parametrize("case", ["V", "F"])
+@pytest.mark.parametrize("case", ["V", "F", "H", "E"])
 def test_adjoint_is_exactly_linear(refs, case):
     seeds = refs.usable(case)[:5]
     sv, Ps = _solved(refs, case, seeds)
@@ -235,12 +235,12 @@ def test_without_b_the_rest_is_unchanged_and_b_is_not_touched(refs):
 
 
 # ------------------------------------------------------------------------------------------- 6: the feedback gain
-def test_feedback_gain_adjoint_against_the_oracle(refs):
-    case = "F"
+@pytest.mark.parametrize("case,nx0,shape", TT.GAIN_CASES, ids=[c[0] for c in TT.GAIN_CASES])
+def test_feedback_gain_adjoint_against_the_oracle(refs, case, nx0, shape):
     seeds = refs.usable(case)
     sv, Ps = _solved(refs, case, seeds)
-    nu0, nx1, nx0 = Ps[0]["nu"][0], Ps[0]["nx"][1], 3
-    assert Ps[0]["nx"][0] == 0 and (nu0, nx1) == (3, 8)
+    nu0, nx1 = Ps[0]["nu"][0], Ps[0]["nx"][1]
+    assert Ps[0]["nx"][0] == 0 and (nu0, nx1) == shape
     rng = np.random.default_rng(11)
     A0, S0 = rng.standard_normal((len(Ps), nx1, nx0)), rng.standard_normal((len(Ps), nu0, nx0))
     K = sv.feedback_gain_adjoint(A0, S0).cpu().numpy()
@@ -255,13 +255,14 @@ def test_feedback_gain_adjoint_against_the_oracle(refs):
             gate = refs.tan.gate(ref, alt)
             err = TC.rel(K[p, :, i], ref["u"][:nu0])
             worst = max(worst, err)
-            assert err <= gate, (seed, i, err, gate)
-    print("gain: worst relative error", worst)
+            assert err <= gate, (case, seed, i, err, gate)
+    print("gain", case, "worst relative error", worst)
     # a gain shared by every problem: (nx1, nx0) / (nu0, nx0) blocks
     K1 = sv.feedback_gain_adjoint(A0[0], S0[0]).cpu().numpy()
     assert _same(K1[0], K[0])
-    # x0_gradient is the chain rule on the call's own outputs.  Its sum has nx1 + nu0 = 11 products, so it agrees with
-    # numpy's to 11 roundings of the absolute sum, whatever the summation order: 16 eps (|A0|' |gb_0| + |S0|' |gr_0|)
+    # x0_gradient is the chain rule on the call's own outputs.  Its sum has nx1 + nu0 = 11 (H: 16) products, so it
+    # agrees with numpy's to that many roundings of the absolute sum, whatever the summation order, and a rounding is
+    # eps / 2: within 16 eps (|A0|' |gb_0| + |S0|' |gr_0|)
     gu = np.zeros((len(Ps), nu0, sv.sizes["u"]))
     gu[:, np.arange(nu0), np.arange(nu0)] = 1.0
     grads = sv.adjoint({"u": _dev(sv, gu)}, nu0, want=("b", "r"))

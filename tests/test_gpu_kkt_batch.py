@@ -2,12 +2,12 @@
 BatchSolver.kkt_new_rhs, OcpBatchSolver.resolve / kkt_sets) on the GPU against the CPU oracle's
 d_kkt_solve_new_rhs_res_mpc_hard_tv.
 
-Inputs: the cases V, V0, F, S of ocp_batch_cases with seeds 0..9.  The "tightened" problems have lb, ub, lg, ug
-multiplied by 0.25 and are solved with mu0 = 2, mu_tol = 1e-4, alpha_min = 1e-8, k_max = 50: the untightened random
-problems end with every |lam| < 1e-5, which would leave the constraint half of the re-solve untested, and at
-mu_tol = 1e-10 the 1/t terms of the last Newton system spread the oracle's own two builds by up to 4e-4.  Every
-test on tightened problems asserts its preconditions (`usable`): only problems with oracle status != 0 are left out
-and at most 1 of 10 per case; the two oracle builds (liboracle.so, liboracle_fma.so) agree on kk and their re-solves
+Inputs: the cases V, V0, F, S, H, E, B of ocp_batch_cases with seeds 0..9.  The "tightened" problems have lb, ub, lg,
+ug multiplied by 0.25 and are solved with mu0 = 2, mu_tol = 1e-4, alpha_min = 1e-8, k_max = 50: the untightened
+random problems end with every |lam| < 1e-5, which would leave the constraint half of the re-solve untested, and at
+mu_tol = 1e-10 the 1/t terms of the last Newton system spread the oracle's own two builds by up to 4e-4.  Every test
+on tightened problems asserts its preconditions (`usable`): only problems with oracle status != 0 are left out and
+at most 1 of 10 per case; the two oracle builds (liboracle.so, liboracle_fma.so) agree on kk and their re-solves
 differ by at most TOL_IPM / 4 on every problem and right-hand side used; at least 8 of 10 problems (S: 5 of 10) end
 with a multiplier above 1e-2.  Gates: TOL_IPM = 1e-10 relative to max(1, |ref|), inf_norm_res 1e-9 absolute; the
 untightened test uses the GATES rule max(TOL_IPM, 4 x the spread of the oracle's builds).
@@ -28,7 +28,8 @@ SENTINEL = -7.25
 SEEDS = range(10)
 TIGHT = dict(mu0=2.0, mu_tol=1e-4, alpha_min=1e-8)
 LOOSE = dict(mu0=2.0, mu_tol=1e-10, alpha_min=1e-8)
-MIN_ACTIVE = {"V": 8, "V0": 8, "F": 8, "S": 5}  # problems (of 10) that must end with a multiplier above 1e-2
+# problems (of 10) that must end with a multiplier above 1e-2
+MIN_ACTIVE = {"V": 8, "V0": 8, "F": 8, "S": 5, "H": 8, "E": 8, "B": 8}
 
 
 def fma_oracle():
@@ -160,21 +161,23 @@ def _as_iterate(h, p, r):
 
 # ------------------------------------------------------------------------------------------ 1: the OCP route
 @pytest.mark.parametrize("order", ["C", "F"])
-@pytest.mark.parametrize("case", ["V", "V0", "F", "S"])
+@pytest.mark.parametrize("case", ["V", "V0", "F", "S", "H", "E", "B"])
 def test_ocp_resolve_matches_the_wrapper(refs, oracle, case, order):
     seeds = refs.usable(case)
     sv, Ps, ipms = _solved(refs, case, seeds, order)
     P2s = [refs.kkt(case, s, True, 6)[0] for s in seeds]
     sv.resolve(to_device(sv, flatten_problems(P2s, order)))
     got = sv.results()
+    worst = 0.0
     for p, (P, P2, g) in enumerate(zip(Ps, P2s, got)):
         ref = IO.kkt_ocp(oracle, P, P2, k_max=K_MAX, mu0=TIGHT["mu0"], mu_tol=TIGHT["mu_tol"])
         ref.update(status=ipms[p][1]["ret"], kk=ipms[p][1]["kk"])  # the IPM's: the re-solve has none of its own
-        check(g, ref, keys=("u", "x", "pi", "lam"), tag=(case, order, seeds[p]))
+        worst = max(worst, check(g, ref, keys=("u", "x", "pi", "lam"), tag=(case, order, seeds[p])))
+    print(case, order, "worst relative error of the re-solve", worst)
 
 
 # ------------------------------------------------------------------------ 2: untightened, mu_tol = 1e-10
-@pytest.mark.parametrize("case", ["V", "F"])
+@pytest.mark.parametrize("case", ["V", "F", "H", "E"])
 def test_ocp_resolve_untightened(refs, case):
     seeds = [s for s in SEEDS if refs.ipm(case, s, False)[1]["ret"] == 0]
     assert len(seeds) >= len(SEEDS) - 1
@@ -194,7 +197,7 @@ def test_ocp_resolve_untightened(refs, case):
 
 
 # ------------------------------------------------------------------------------------------------ 3: many sets
-@pytest.mark.parametrize("case", ["V", "F"])
+@pytest.mark.parametrize("case", ["V", "F", "H", "E"])
 def test_many_sets_per_factor(refs, case):
     rseeds = (6, 7, 8)
     seeds = refs.usable(case, rseeds)[:5]

@@ -70,7 +70,8 @@ def _core_dense(sv, Ps, dirs, ndir, **kw):
 
 
 # ------------------------------------------------------------------ 1: against the reference; the call and its parts
-@pytest.mark.parametrize("case,order", [("V", "C"), ("V", "F"), ("F", "C"), ("S", "C")])
+@pytest.mark.parametrize("case,order", [("V", "C"), ("V", "F"), ("F", "C"), ("S", "C"), ("H", "C"), ("H", "F"),
+                                        ("E", "C"), ("E", "F"), ("B", "C"), ("B", "F")])
 def test_tangent_data_matches_the_reference(refs, case, order):
     seeds = refs.usable(case)
     sv, Ps = _solved(refs, case, seeds, order)

@@ -84,9 +84,9 @@ def test_adjoint_data_matches_the_reference(refs, case, order):
 
 # --------------------------------- 2, 3: the combined call is the two calls it is made of; gQ and gR are symmetric
 @pytest.mark.parametrize("order", ["C", "F"])
-@pytest.mark.parametrize("case", ["V", "F"])
+@pytest.mark.parametrize("case", ["V", "F", "H", "E"])
 def test_combined_call_is_bitwise_its_parts_and_symmetric(refs, case, order):
-    seeds = refs.usable(case)[:4]
+    seeds = refs.adj.usable(case)[:4]  # bitwise only: no matrix-gradient reference is needed
     sv, Ps = _solved(refs, case, seeds, order)
     cots = [_cots(refs, case, s, 2) for s in seeds]
     dense = AT._dense_cot(sv, cots)

@@ -24,12 +24,11 @@ def _same(a, b):
     return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
-@pytest.fixture(scope="module")
-def setup():
+def _setup(case):
     """(solver, the dense data tensors of the tightened problems, one random cotangent per output, the problems)"""
     from hpmpc_amd.ocp_autograd import ocp_solve  # noqa: F401  (the module imports without torch loaded by it)
 
-    Ps = [KB.tighten(P) for P in problems(CASE, SEEDS)]
+    Ps = [KB.tighten(P) for P in problems(case, SEEDS)]
     sv = make_solver(Ps, "C")
     data = to_device(sv, flatten_problems(Ps, "C"))
     rng = np.random.default_rng(3)
@@ -37,6 +36,11 @@ def setup():
     size = dict(u=s["u"], x=s["x"], pi=s["pi_out"], lam=s["lam_out"], t=s["lam_out"])
     cot = {k: sv.torch.from_numpy(rng.standard_normal((len(Ps), size[k]))).to(sv.dev) for k in OUT_KEYS}
     return sv, data, cot, Ps
+
+
+@pytest.fixture(scope="module")
+def setup():
+    return _setup(CASE)
 
 
 def _leaves(data, needs=KEYS):
@@ -69,7 +73,7 @@ def test_forward_is_pack_solve_finish(setup):
     assert sv2.kk.tolist() == sv.kk.tolist()
 
 
-def test_backward_is_adjoint_data_bit_for_bit(setup):
+def _backward_is_adjoint_data(setup):
     from hpmpc_amd.ocp_autograd import ocp_solve
 
     sv, data, cot, _ = setup
@@ -82,6 +86,16 @@ def test_backward_is_adjoint_data_bit_for_bit(setup):
         g = leaves[key].grad
         assert g is not None and g.shape == data[key].shape and _same(g, ref[key]), key
     assert min(float(leaves[key].grad.abs().max()) for key in KEYS) > 1e-6
+
+
+def test_backward_is_adjoint_data_bit_for_bit(setup):
+    _backward_is_adjoint_data(setup)
+
+
+def test_backward_is_adjoint_data_bit_for_bit_at_the_tile_edge():
+    """Case E: 16 x 16 blocks of A and Q, 16 rows of C, nu = 0 on an inner stage -- the largest arrays the layer sees.
+    A test of its own, so that the V test keeps its id."""
+    _backward_is_adjoint_data(_setup("E"))
 
 
 def test_shared_input_gets_the_sum_over_problems(setup):

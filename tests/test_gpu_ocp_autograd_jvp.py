@@ -43,8 +43,8 @@ def _jvp(sv, data, tans):
         return [p.primal.clone() for p in pairs], [None if p.tangent is None else p.tangent.clone() for p in pairs]
 
 
-def test_jvp_is_bitwise_tangent_data(refs):
-    sv, Ps, data = _setup(refs, "V", 4)
+def _jvp_is_tangent_data(refs, case):
+    sv, Ps, data = _setup(refs, case, 4)
     keys = ("A", "B", "Q", "R", "C", "D", "b", "q", "lb", "ug")  # S, r, ub, lg: no tangent, they do not move
     tans = _tangents(sv, data, keys, 3)
     primal, tangent = _jvp(sv, data, tans)
@@ -59,6 +59,16 @@ def test_jvp_is_bitwise_tangent_data(refs):
     out = sv.finish()
     for key, p in zip(OUT_KEYS, primal):
         assert _same(p.cpu().numpy(), out[key].cpu().numpy()), key
+
+
+def test_jvp_is_bitwise_tangent_data(refs):
+    _jvp_is_tangent_data(refs, "V")
+
+
+def test_jvp_is_bitwise_tangent_data_at_the_tile_edge(refs):
+    """Case E: 16 x 16 blocks of A and Q, 16 rows of C, nu = 0 on an inner stage -- the largest arrays the layer sees.
+    A test of its own, so that the V test keeps its id."""
+    _jvp_is_tangent_data(refs, "E")
 
 
 def test_a_shared_input_and_inputs_without_tangent(refs):

@@ -40,7 +40,7 @@ def refs(oracle):
 
 # ------------------------------------------------------------------------------------------------------- 1 .. 4: pack
 @pytest.mark.parametrize("order", ["C", "F"])
-@pytest.mark.parametrize("case", ["V", "F"])
+@pytest.mark.parametrize("case", ["V", "F", "H", "E", "B"])
 def test_pack_is_bitwise(case, order):
     Ps = problems(case, range(70))  # 70 problems: more than any per-workgroup grouping
     sv = make_solver(Ps, order)
@@ -126,14 +126,14 @@ def test_pack_shared_arrays():
 
 # --------------------------------------------------------------------------------------------------- 5 .. 8: solves
 @pytest.mark.parametrize("order", ["C", "F"])
-@pytest.mark.parametrize("case", ["V0", "F", "S"])
+@pytest.mark.parametrize("case", ["V0", "F", "S", "H", "B"])
 def test_solve_parity(refs, case, order):
     seeds = (1, 2, 3)
     Ps, ref = zip(*[refs(case, s) for s in seeds])
     assert all(r["status"] == 0 for r in ref)
     sv, got = solve_batch(list(Ps), order)
-    for p, (g, r) in enumerate(zip(got, ref)):
-        check(g, r, tag=(case, order, p))
+    worst = max(check(g, r, tag=(case, order, p)) for p, (g, r) in enumerate(zip(got, ref)))
+    print(case, order, "worst relative error of the solve", worst)
 
 
 @pytest.mark.parametrize("order", ["C", "F"])
@@ -155,21 +155,33 @@ def test_warm_start(oracle):
         check(g, r, tag=p)
 
 
-def test_equality_box(oracle):
-    Ps = problems("F", (6, 7))
+def _equality_boxes(case, fixed):
+    """Stage 1's input boxes `fixed` with lb == ub: finish returns lb there, and the iterate's bits everywhere else."""
+    Ps = problems(case, (6, 7))
     for P in Ps:
         P["ub"][1] = P["ub"][1].copy()
-        P["ub"][1][1] = P["lb"][1][1]  # input 1 of stage 1: lb == ub
-    assert Ps[0]["hidxb"][1][1] == 1 and Ps[0]["nu"][1] > 1
+        P["ub"][1][fixed] = P["lb"][1][fixed]  # inputs `fixed` of stage 1: lb == ub
+    assert list(Ps[0]["hidxb"][1][fixed]) == fixed and Ps[0]["nu"][1] > max(fixed)
     sv, got = solve_batch(Ps, "F")
     ux = sv.ux.cpu().numpy().reshape(len(Ps), -1, 16)
     for p, (P, g) in enumerate(zip(Ps, got)):
-        assert g["u"][1][1] == P["lb"][1][1]
+        assert np.array_equal(g["u"][1][fixed], P["lb"][1][fixed])
         # every other entry is the iterate's
         for k in range(P["N"]):
-            keep = [j for j in range(P["nu"][k]) if (k, j) != (1, 1)]
+            keep = [j for j in range(P["nu"][k]) if k != 1 or j not in fixed]
             assert np.array_equal(_bits(g["u"][k][keep]), _bits(ux[p, k, keep]))
             assert np.array_equal(_bits(g["x"][k]), _bits(ux[p, k, P["nu"][k]:P["nu"][k] + P["nx"][k]]))
+        assert np.array_equal(_bits(g["x"][P["N"]]), _bits(ux[p, P["N"], :P["nx"][P["N"]]]))
+
+
+def test_equality_box(oracle):
+    _equality_boxes("F", [1])
+
+
+def test_equality_box_on_every_input(oracle):
+    """B's stage 1: nu = 8 with all eight inputs boxed and every one an equality, so the fix loop of the unpack runs its
+    nbu = 8 times and no input of the stage is left to the iterate."""
+    _equality_boxes("B", list(range(8)))
 
 
 # ------------------------------------------------------------------------------------------- 9, 10: refusals, tile plan
@@ -274,7 +286,7 @@ def test_range_and_null_refusals_of_every_call():
 
 
 def test_sizes_and_offsets_match_the_host_layout(refs):
-    for case in ("V", "F"):
+    for case in ("V", "F", "H", "E", "B"):
         P = problems(case, [1])[0]
         sv = make_solver([P], "C")
         lay = ocp_dense_layout(P["N"], P["nx"], P["nu"], P["nb"], P["ng"])
@@ -322,12 +334,13 @@ def test_tile_plan_runs_the_existing_batched_call(refs):
 
 # --------------------------------------------------------------------------- 11, 12: one placement for every unpack / pack
 @pytest.mark.parametrize("order", ["C", "F"])
-def test_finish_equals_the_one_set_unpack(order):
+@pytest.mark.parametrize("case", ["V", "E"])
+def test_finish_equals_the_one_set_unpack(case, order):
     """hpmpc_mi355x_ocp_finish_batch and hpmpc_mi355x_ocp_unpack_sets(nrhs = 1) run one kernel: on the solver's own d,
     ux, pi, lam, t they give the same u, x (equality-box fix included), pi, lam, t bit for bit, and neither writes t
     when t_out is null."""
     L = ocp_lib()
-    Ps = problems("V", range(4))
+    Ps = problems(case, range(4))
     P = Ps[1]
     P["ub"][0] = P["ub"][0].copy()
     P["ub"][0][0] = P["lb"][0][0]  # input box 0 of stage 0: lb == ub

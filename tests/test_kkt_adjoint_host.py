@@ -51,7 +51,7 @@ def test_built_library_exports_them():
     assert L.hpmpc_mi355x_last_error() == -10
 
 
-@pytest.mark.parametrize("case", ["V", "S"])
+@pytest.mark.parametrize("case", ["V", "S", "H", "E", "B"])
 def test_adjoint_set_arrays_is_the_transpose_of_the_dense_placement(case):
     """<dense_of(P, it), g> == <it, adjoint_set_arrays(g)> exactly, on integer-valued data (every sum is exact)."""
     rng = np.random.default_rng(5)
@@ -78,7 +78,8 @@ def test_adjoint_set_arrays_is_the_transpose_of_the_dense_placement(case):
 def test_reference_preconditions(refs, case):
     """Measured on liboracle.so / liboracle_fma.so: left out only F seed 2; 89 to 132 columns per problem; build
     spread of the reference adjoint <= 1.8e-12 (gated at TOL_IPM / 4 = 2.5e-11); problems with max |dbar_ref| >= 1e-2:
-    V 10/10, V0 10/10, F 9/9, S 10/10."""
+    V 10/10, V0 10/10, F 9/9, S 10/10.  H, E, B (the wide cases): 220 / 276 / 180 columns, spread <= 1.2e-11 / 1.7e-12
+    / 5.4e-13, 10/10 each."""
     rows = refs.measure(case)
     print(case, [(r["seed"], r["ncol"], r["spread"], r["dbar"]) for r in rows])
     used = refs.usable(case)
@@ -101,11 +102,18 @@ def _index_sets(P, sizes):
     return np.array(row["lb"] + row["lg"], dtype=int), np.array(row["ub"] + row["ug"], dtype=int)
 
 
-@pytest.mark.parametrize("case", ["V", "S"])
+@pytest.mark.parametrize("case", ["V", "S", "B"])
 def test_three_step_formula_reproduces_the_reference(refs, case):
     """h = gt - w glam, c = h_lo - h_up; (y_ux, y_pi) = S(gux + C' c, gpi); qbar = y_ux, bbar = y_pi, z = C y_ux,
     dbar_lo = -h_lo - w_lo z, dbar_up = h_up - w_up z -- with S, w and C all read off T_ref itself: S its (u, x, pi) x
-    (r, q, b) block, w = -dlam / dt on each slot's own bound column, C from dt_lo = C dux over the (r, q, b) columns."""
+    (r, q, b) block, w = -dlam / dt on each slot's own bound column, C from dt_lo = C dux over the (r, q, b) columns.
+
+    Not run at H and E.  This restatement recovers w and C from T_ref by least squares, so T_ref's own rounding (the two
+    builds differ by up to 1.2e-11 at H) enters twice and is multiplied by w.  Measured: every seed of V, S and B is
+    under 7e-12, H has 2.0e-11 on seed 2 and 9.5e-11 on seed 5, E has 1.9e-11 on seed 4 and 4.3e-10 on seed 8 -- above
+    this test's TOL_IPM / 4, while the reference adjoint T_ref' g that the GPU tests compare with spreads by at most
+    1.2e-11 / 1.7e-12 between the builds at H / E (test_reference_preconditions).  The bound is kept and the two cases
+    are left out, not the other way round: what fails there is this way of reading w off T_ref, not the reference."""
     for seed in refs.usable(case):
         P = refs.ipm(case, seed)[0]
         T = refs.matrix(case, seed)[0]

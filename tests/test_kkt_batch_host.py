@@ -21,7 +21,7 @@ import iface_oracle as IO  # noqa: E402
 ENTRY_POINTS = ("hpmpc_mi355x_kkt_scratch_doubles", "hpmpc_mi355x_kkt_new_rhs_batch", "hpmpc_mi355x_ocp_kkt_batch")
 
 
-@pytest.mark.parametrize("case", ["V", "S"])
+@pytest.mark.parametrize("case", ["V", "S", "H", "E", "B"])
 def test_set_arrays_match_the_oracle_helpers(case):
     """b, q against hpmpc_amd.cabi.bq_from_qp of the packed problem and d against to_qp's d, element for element;
     everything beyond them (the padding of the 16- / 32-double stage slots, b at stage N) is zero."""

@@ -55,7 +55,8 @@ def test_built_library_exports_them():
 def test_reference_preconditions(refs, case):
     """Measured on liboracle.so / liboracle_fma.so: the seeds are TanRefs.usable's (only F seed 2 left out); build spread
     of the reference tangents <= 2.1e-12 (gated at TOL_IPM / 4 = 2.5e-11) with SCALE = 1; on V every problem has max
-    |dlam_ref| >= 0.2 and the C / D direction alone moves the residuals by >= 0.17 / >= 0.08."""
+    |dlam_ref| >= 0.2 and the C / D direction alone moves the residuals by >= 0.17 / >= 0.08.  H, E, B: none left out,
+    spread <= 1.3e-11 / 2.6e-12 / 5.1e-13; on E |dlam_ref| >= 1.1 and the C / D moves are >= 0.58 / >= 0.21."""
     rows = refs.measure(case)
     print(case, [(r["seed"], r["spread"], r["dlam"], r["dFC"], r["dFD"]) for r in rows])
     used = refs.usable(case)

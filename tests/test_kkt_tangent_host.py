@@ -43,7 +43,7 @@ def test_built_library_exports_them():
     assert L.hpmpc_mi355x_last_error() == -10
 
 
-@pytest.mark.parametrize("case", ["V", "S"])
+@pytest.mark.parametrize("case", ["V", "S", "H", "E", "B"])
 def test_tangent_set_arrays_is_the_difference_of_kkt_set_arrays(case):
     Ps = problems(case, (0, 1, 2))
     rng = np.random.default_rng(3)
@@ -85,7 +85,8 @@ def test_x0_directions_are_the_columns():
 def test_reference_preconditions(oracle, case):
     """Measured on liboracle.so / liboracle_fma.so: left out only F seed 2 (ret 1); build spread <= 6.9e-13 and
     affinity defect <= 1.3e-12 (both gated at TOL_IPM / 4 = 2.5e-11); problems with max |dlam_ref| >= 1e-2: V 10/10,
-    V0 10/10, F 9/9, S 8/10."""
+    V0 10/10, F 9/9, S 8/10.  H, E, B (the wide cases): none left out, spread <= 8.0e-13, defect <= 8.3e-13, 10/10
+    each."""
     refs = TC.TanRefs(oracle)
     rows = refs.measure(case)
     print(case, [(r["seed"], r["ret"], r.get("spread"), r.get("affinity"), r.get("dlam")) for r in rows])

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from hpmpc_amd.ocp_batch import KEYS, flatten_problems, ocp_dense_layout, unflatten_problems
+from ocp_batch_cases import CASES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -20,9 +21,10 @@ NEW = ("hpmpc_mi355x_ocp_plan_create", "hpmpc_mi355x_ocp_plan_destroy", "hpmpc_m
 # N, nx, nu, boxed inputs, boxed states, ng
 V = (5, [0, 3, 3, 5, 5, 4], [2, 2, 1, 3, 3], 2, 2, [0, 0, 2, 0, 3, 2])
 F = (4, [0, 8, 8, 8, 8], [3, 3, 3, 3], 3, 4, None)
+H, E, B = (CASES[c] for c in "HEB")  # the (4, 12) class, the 16-wide tile edge, all boxes
 
 
-@pytest.mark.parametrize("case", [V, F], ids=["V", "F"])
+@pytest.mark.parametrize("case", [V, F, H, E, B], ids=["V", "F", "H", "E", "B"])
 @pytest.mark.parametrize("order", ["C", "F"])
 def test_flatten_round_trip_is_exact(case, order):
     Ps = [IO.random_iface_problem(*case, seed=s) for s in (1, 2, 3)]
@@ -86,6 +88,29 @@ def test_layout_equals_the_written_out_sums():
     assert list(off["D"]) == [0, 0, 0, 2, 2, 11] and sz["D"] == 11
     assert list(off["lam"]) == [0, 4, 12, 22, 30, 44] and sz["lam"] == 52
     assert list(off["u"]) == list(off["r"]) and list(off["x"]) == list(off["q"]) and list(off["pi"]) == list(off["b"])
+
+
+def test_wide_cases_sit_on_the_tile_edge():
+    """What H, E and B are in the table for, read off the problems IO.random_iface_problem makes of them: the stage
+    sizes at which a 16-double ux / pi slot or a 32-double lam / t slot is full."""
+    r4 = lambda n: (n + 3) // 4 * 4
+    slots = lambda P: [2 * r4(b) + 2 * r4(g) for b, g in zip(P["nb"], P["ng"])]
+    Ph, Pe, Pb = (IO.random_iface_problem(*c, seed=1) for c in (H, E, B))
+    # H: (nu, nx) = (4, 12) on every inner stage, an empty x_0, nb = 8 on the inner stages
+    assert Ph["nx"][0] == 0 and all((Ph["nu"][k], Ph["nx"][k]) == (4, 12) for k in range(1, 5))
+    assert Ph["nb"] == [4, 8, 8, 8, 8, 4] and not any(Ph["ng"])
+    # E: every stage fills the 32 slots, in the splits 4 + 12, 8 + 8 (both padded), 8 + 8, 8 + 8, 0 + 16
+    assert slots(Pe) == [32] * 5
+    assert list(zip(Pe["nb"], Pe["ng"])) == [(4, 12), (5, 7), (8, 8), (8, 8), (0, 16)]
+    assert [u + x for u, x in zip(Pe["nu"], Pe["nx"])] == [8, 16, 16, 16, 16] and Pe["nu"][2] == 0
+    assert Pe["nx"][0] > 0 and Pe["ng"][0] > 0          # a variable x_0 under general constraints
+    assert list(Pe["hidxb"][3]) == list(range(8))       # stage 3: every box on an input
+    # B: every variable of stages 1 and 2 boxed, lam / t full; stage 0 with nx 4 and nb 12
+    assert Pb["nb"] == [12, 16, 16, 8] and slots(Pb)[1:3] == [32, 32] and (Pb["nu"][1], Pb["nx"][1]) == (8, 8)
+    lay = ocp_dense_layout(Pe["N"], Pe["nx"], Pe["nu"], Pe["nb"], Pe["ng"])
+    assert lay["sizes"]["lam"] == 2 * sum(Pe["nb"]) + 2 * sum(Pe["ng"]) == 152
+    assert lay["sizes"]["C"] == 12 * 4 + 7 * 12 + 8 * 16 + 8 * 8 + 16 * 16
+    assert lay["sizes"]["D"] == 12 * 4 + 7 * 4 + 0 + 64
 
 
 def test_header_declares_and_export_map_lists_the_new_functions():
