@@ -138,6 +138,70 @@ def mass_spring_soft(N: int, nx: int, nu: int, *, x0=None, Zq: float = 0.0, zl: 
     return SoftQP(N, nxv, nuv, nbv, nsv, idxb, BAbt, RSQrq, dv, Zv, zv)
 
 
+def random_soft_qp(N: int, nx, nu, nb, ns, *, seed: int, structure_seed: int = 0, x0_scale: float = 2.0,
+                   Zq: float = 0.5, zl: float = 10.0) -> SoftQP:
+    """Random soft-constrained QP with per-stage sizes (lists of length N + 1; nu[N] is forced to 0): what
+    mass_spring_soft fixes is drawn here.
+    ``idxb[k]``: nb[k] + ns[k] distinct variables of the nu + nx, drawn by ``structure_seed`` alone (a batch shares
+    idxb while its data differ); the hard part and the soft part are each sorted, so the whole is in general not
+    monotone, and either part may pick inputs or states.
+    Data (``seed``): A = I + 0.1 randn / sqrt(nx) (rectangular where nx changes), B = 0.3 randn, b = 0.05 randn --
+    ``x0_scale`` randn on stage 0 when nx[0] = 0, where b stands for A x0; dense SPD stage Hessians G G' / n + I with
+    their S block and a gradient 0.5 randn; hard bounds -+(0.5..1.5), soft bounds -+(0.8..1.2); Z = Zq (0.5..1.5)
+    and z = zl (0.5..1.5) per element.
+    Asserts what the product requires: the tile plan's limits on nb + ns boxes (hpmpc_capi.cpp plan_supported) and
+    the b_k read inside BAbt_k (hpmpc_capi_soft.cpp soft_unsupported)."""
+    nxv = np.asarray(nx, dtype=np.int32).copy()
+    nuv = np.asarray(nu, dtype=np.int32).copy()
+    nbv = np.asarray(nb, dtype=np.int32).copy()
+    nsv = np.asarray(ns, dtype=np.int32).copy()
+    assert N >= 1 and all(len(v) == N + 1 for v in (nxv, nuv, nbv, nsv))
+    nuv[N] = 0
+    for k in range(N + 1):
+        nuk, nxk, nbs = int(nuv[k]), int(nxv[k]), int(nbv[k] + nsv[k])
+        assert nuk >= 0 and nxk >= 0 and nuk + nxk <= 16 and rup(nuk, 4) + nxk <= 16, (k, "stage beyond the tile")
+        assert nbv[k] >= 0 and nsv[k] >= 0 and nbs <= nuk + nxk and rup(nbs, 4) <= 16, (k, "boxes beyond the plan")
+        if k < N and nxv[k + 1] > 0:  # b_k is read with the reference's stride round_up(nx', 4) (d_ip2_soft.c:172)
+            nux, nx1 = nuk + nxk, int(nxv[k + 1])
+            assert (nux // 4) * 4 * rup(nx1, 4) + nux % 4 + 4 * (nx1 - 1) < rup(nux + 1, 4) * rup(nx1, 2), \
+                (k, "b_k read outside BAbt_k")
+    srng = np.random.Generator(np.random.PCG64(structure_seed))
+    rng = np.random.Generator(np.random.PCG64(seed))
+    BAbt, RSQrq, dv, idxb, Zv, zv = [], [], [], [], [], []
+    for k in range(N + 1):
+        nuk, nxk, nbk, nsk = int(nuv[k]), int(nxv[k]), int(nbv[k]), int(nsv[k])
+        nux = nuk + nxk
+        pick = srng.permutation(nux)[:nbk + nsk]
+        ib = np.concatenate([np.sort(pick[:nbk]), np.sort(pick[nbk:])]).astype(np.int32)
+        idxb.append(ib if ib.size else np.zeros(1, dtype=np.int32))
+        if k < N:
+            nx1 = int(nxv[k + 1])
+            M = np.zeros((nux + 1, nx1))
+            M[:nuk] = 0.3 * rng.standard_normal((nuk, nx1))
+            M[nuk:nux] = (np.eye(nx1, nxk) + 0.1 * rng.standard_normal((nx1, nxk)) / np.sqrt(max(nxk, 1))).T
+            M[nux] = (x0_scale if k == 0 and nxk == 0 else 0.05) * rng.standard_normal(nx1)
+            BAbt.append(pack_lib4_batch(M[None])[0].copy())
+        G = rng.standard_normal((nux, nux))
+        M = np.zeros((nux + 1, nux))
+        M[:nux] = G @ G.T / max(nux, 1) + np.eye(nux)
+        M[nux] = 0.5 * rng.standard_normal(nux)
+        RSQrq.append(pack_lib4_batch(M[None])[0].copy())
+        pnb, pns = rup(nbk, 4), rup(nsk, 4)
+        dk = np.zeros(2 * pnb + 2 * pns + 4)
+        dk[:nbk] = -(0.5 + rng.random(nbk))
+        dk[pnb:pnb + nbk] = 0.5 + rng.random(nbk)
+        dk[2 * pnb:2 * pnb + nsk] = -(0.8 + 0.4 * rng.random(nsk))
+        dk[2 * pnb + pns:2 * pnb + pns + nsk] = 0.8 + 0.4 * rng.random(nsk)
+        dv.append(dk)
+        Zk, zk = np.zeros(2 * pns + 4), np.zeros(2 * pns + 4)
+        for o in (0, pns):
+            Zk[o:o + nsk] = Zq * (0.5 + rng.random(nsk))
+            zk[o:o + nsk] = zl * (0.5 + rng.random(nsk))
+        Zv.append(Zk)
+        zv.append(zk)
+    return SoftQP(N, nxv, nuv, nbv, nsv, idxb, BAbt, RSQrq, dv, Zv, zv)
+
+
 # ------------------------------------------------------------------------------------------------
 # Batched, device-resident soft-constraint IPM (hpmpc_mi355x_ipm_soft_batch, include/hpmpc_mi355x.h): a batch is
 # a list of SoftQPs that share stage sizes and idxb.  Problem-major arrays, every stage in the reference's layout:

@@ -785,6 +785,53 @@ def soft(ref, out):
         outs = dict(ux=r["ux"], pi=r["pi"], lam=r["lam"], t=r["t"], stat=r["stat"], kk=r["kk"], ret=r["ret"])
         out.append(save_case(f"soft_{name}", "soft", sq, args, outs,
                              extra=dict(ns=[sq.ns.astype(np.float64)], Z=sq.Z, z=sq.z)))
+    soft_random_structure(ref, out)
+
+
+def soft_random_structure(ref, out):
+    """soft_rs_<case>: the cases of tests/soft_cases.py (random_soft_qp: scattered idxb, soft boxes on inputs, stage
+    sizes that change, a variable x_0, stray soft-gradient writes into later stages' live slots) at the first
+    admitted seed of each, with that module's arguments (mu_tol 1e-6); `odd` also warm-started."""
+    import soft_cases as SC
+
+    def save(name, sq, args, r, extra):
+        outs = dict(ux=r["ux"], pi=r["pi"], lam=r["lam"], t=r["t"], stat=r["stat"], kk=r["kk"], ret=r["ret"])
+        out.append(save_case(name, "soft", sq, args, outs,
+                             extra=dict(ns=[sq.ns.astype(np.float64)], Z=sq.Z, z=sq.z, **extra)))
+
+    for name in SC.CASES:
+        seed, kk, ret, _ = SC.CASES[name]["draws"][0]
+        sq = SC.make(name, seed)
+        r = ref.ipm_soft(sq.copy(), work_extra=1 << 16, **SC.ARGS)
+        assert (r["kk"], r["ret"]) == (kk, ret), (name, r["kk"], r["ret"])
+        save(f"soft_rs_{name}", sq, SC.ARGS, r, {})
+        if name == "odd":
+            ux0 = SC.warm_ux(sq)
+            r = ref.ipm_soft(sq.copy(), work_extra=1 << 16, warm_start=1, ux=ux0, **SC.ARGS)
+            assert r["ret"] == 0, r["ret"]
+            save("soft_rs_odd_warm", sq, dict(SC.ARGS, warm_start=1), r, dict(ux0=ux0))
+
+
+def soft_admission(ref, nseed=8):
+    """How the draws of tests/soft_cases.py were admitted: every case at seeds 0 .. nseed-1 through the reference's
+    c99 build, the oracle and the oracle's FMA build; prints kk / ret of each and the oracle builds' spread and the
+    oracle-to-reference distance as shares of the worst TOL_SOFT gate.  A draw is admitted when the three agree on
+    kk / ret, the spread is at most soft_cases.ADMIT and the run converges (or takes the early exit of x0_box)."""
+    import soft_cases as SC
+
+    orc = HpmpcAPI(load(os.path.join(ROOT, "oracle", "liboracle.so")), "orc_")
+    fma = HpmpcAPI(load(os.path.join(ROOT, "oracle", "liboracle_fma.so")), "orc_")
+    for name in SC.CASES:
+        for seed in range(nseed):
+            sq = SC.make(name, seed)
+            r = ref.ipm_soft(sq.copy(), work_extra=1 << 16, **SC.ARGS)
+            o, f = orc.ipm_soft(sq.copy(), **SC.ARGS), fma.ipm_soft(sq.copy(), **SC.ARGS)
+            same = (r["kk"], r["ret"]) == (o["kk"], o["ret"]) == (f["kk"], f["ret"])
+            sp = max(SC.gate_share(SC.soft_errors(sq, f, o)).values())
+            er = max(SC.gate_share(SC.soft_errors(sq, o, r)).values())
+            ok = same and sp <= SC.ADMIT and (o["ret"] == 0 or (name == "x0_box" and o["ret"] == 2 and o["kk"] <= 4))
+            print(f"  {name:9s} seed {seed}: kk {r['kk']} / {o['kk']} / {f['kk']}, ret {r['ret']} / {o['ret']} / "
+                  f"{f['ret']}, spread {sp:.1e}, oracle to reference {er:.1e}{'  admitted' if ok else ''}")
 
 
 if __name__ == "__main__":
@@ -792,6 +839,12 @@ if __name__ == "__main__":
         o = []
         soft(ref_api(), o)
         print(f"wrote {len(o)} soft cases, {sum(os.path.getsize(p) for p in o) / 1e6:.2f} MB")
+    elif len(sys.argv) > 1 and sys.argv[1] == "soft_rs":
+        o = []
+        soft_random_structure(ref_api(), o)
+        print(f"wrote {len(o)} soft_rs cases, largest {max(os.path.getsize(p) for p in o)} B")
+    elif len(sys.argv) > 1 and sys.argv[1] == "soft_admission":
+        soft_admission(ref_api())
     elif len(sys.argv) > 1 and sys.argv[1] == "iface":
         o = []
         iface(ref_api(), o)

@@ -84,8 +84,9 @@ def run_case(api, case):
     if case.kind == "soft":
         from hpmpc_amd.soft import SoftQP
 
+        kw = dict(warm_start=1, ux=inp["ux0"]) if a.get("warm_start") else {}
         r = api.ipm_soft(SoftQP.from_case(case), k_max=int(a["k_max"]), mu0=a["mu0"], mu_tol=a["mu_tol"],
-                         alpha_min=a["alpha_min"])
+                         alpha_min=a["alpha_min"], **kw)
         return dict(ux=r["ux"], pi=r["pi"], lam=r["lam"], t=r["t"], stat=r["stat"], kk=r["kk"], ret=r["ret"])
     raise ValueError(case.kind)
 

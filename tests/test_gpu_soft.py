@@ -2,13 +2,16 @@
 
 The reference's own outputs pin the oracle (tests/golden/soft_*.npz, run through test_gpu_parity.py as well);
 these cases add sizes and options the goldens do not cover: warm start, iteration caps, time-variant data,
-non-uniform soft sets, and the configurations the product rejects.  Tolerance TOL_SOFT (tests/helpers.py):
+non-uniform soft sets, random stage structure (tests/soft_cases.py: scattered idxb, soft boxes on inputs, changing
+stage sizes, a variable x_0, stray soft-gradient writes into live slots of later stages; the soft_rs_* goldens pin the
+oracle there), and the configurations the product rejects.  Tolerance TOL_SOFT (tests/helpers.py):
 the end game of these problems is rounding-sensitive (the reference's own FMA build drifts from its default
 build by the same amounts), so the cases stop at mu_tol >= 1e-6.
 """
 import numpy as np
 import pytest
 
+import soft_cases as SC
 from helpers import TOL_SOFT
 from hpmpc_amd.soft import mass_spring_soft
 
@@ -67,6 +70,45 @@ def test_soft_warm_start(product, oracle):
     ux0 = [0.05 * rng.standard_normal(sq.nux(k) + 4) for k in range(sq.N + 1)]
     args = dict(k_max=50, mu0=50.0, mu_tol=1e-6, alpha_min=1e-8, warm_start=1, ux=ux0)
     _cmp(sq, product.ipm_soft(sq.copy(), **args), oracle.ipm_soft(sq.copy(), **args))
+
+
+RS = [(name, seed) for name in SC.CASES for seed in SC.seeds(name)]
+
+
+def _shares(tag, sq, got, ref):
+    """Prints the distances _cmp gates as shares of their TOL_SOFT gates (DESIGN.md quotes them)."""
+    share = SC.gate_share(SC.soft_errors(sq, got, ref))
+    print(f"{tag}: kk {got['kk']} ret {got['ret']}, share of gate " + " ".join(f"{k} {v:.2e}" for k, v in share.items()))
+
+
+@pytest.mark.parametrize("name,seed", RS, ids=[f"{n}_s{s}" for n, s in RS])
+def test_soft_random_structure_vs_oracle(product, oracle, name, seed):
+    """Every admitted draw of tests/soft_cases.py (scattered idxb, soft boxes on inputs, changing stage sizes, a
+    variable x_0, stray soft-gradient writes into later stages' live qx slots) against the oracle, kk pinned."""
+    sq = SC.make(name, seed)
+    ref = oracle.ipm_soft(sq.copy(), **SC.ARGS)
+    assert (ref["kk"], ref["ret"]) == [(d[1], d[2]) for d in SC.CASES[name]["draws"] if d[0] == seed][0]
+    got = product.ipm_soft(sq.copy(), **SC.ARGS)
+    _shares(f"single {name} seed {seed}", sq, got, ref)
+    _cmp(sq, got, ref)
+
+
+def test_soft_random_structure_warm_start(product, oracle):
+    sq = SC.make("odd", SC.seeds("odd")[0])
+    args = dict(SC.ARGS, warm_start=1, ux=SC.warm_ux(sq))
+    ref = oracle.ipm_soft(sq.copy(), **args)
+    assert (ref["kk"], ref["ret"]) == (SC.WARM_KK, 0)
+    got = product.ipm_soft(sq.copy(), **args)
+    _shares("single odd warm", sq, got, ref)
+    _cmp(sq, got, ref)
+
+
+def test_soft_rejects_stray_write_into_zl(product):
+    """Boxes and soft boxes on stage N only (nb = ns = 4): the reference's soft-gradient write lands at Zl_N[4..7],
+    which its own loop reads right after (hpmpc_capi_soft.cpp soft_layout)."""
+    sq = SC.refusal_shape()
+    assert SC.soft_stray_targets(sq)[1]
+    assert product.ipm_soft(sq.copy(), k_max=10)["ret"] == EUNSUPPORTED
 
 
 def test_soft_rejects_unsupported(product):

@@ -4,12 +4,14 @@ Every comparison is per problem, against oracle.ipm_soft with k_max=50, mu0=100,
 helpers.TOL_SOFT (ux / t 5e-8, pi / lam 1e-6, stat 1e-7, relative to max(1, |ref|); kk and ret identical) -- the
 comparison of tests/test_gpu_soft.py.  The batches were chosen so that the oracle's own rounding spread (its default
 build against its FMA build) stays under those gates on every gated vector (worst case 12 % of the stat gate); the
-oracle's iteration counts are pinned below, so a change of the inputs shows up as such.  Problem i of a batch has
-x0[0] = x0[1] = s_i.
+oracle's iteration counts are pinned below, so a change of the inputs shows up as such.  Problem i of a mass-spring
+batch has x0[0] = x0[1] = s_i; the rs_* batches are the admitted draws of tests/soft_cases.py (random stage
+structure, spread at most 25 % of every gate by that module's admission rule, worst admitted 8.5 %).
 """
 import numpy as np
 import pytest
 
+import soft_cases as SC
 from helpers import TOL_SOFT
 from hpmpc_amd.soft import (SoftBatchSolver, mass_spring_soft, soft_batch_layout, soft_plan_create)
 from test_gpu_soft import _cmp
@@ -17,6 +19,7 @@ from test_gpu_soft import _cmp
 pytestmark = pytest.mark.gpu
 EUNSUPPORTED = -10
 ARGS = dict(k_max=50, mu0=100.0, mu_tol=1e-6, alpha_min=1e-8)
+assert ARGS == SC.ARGS
 S5 = (0.2, 1.0, 2.0, 3.5, 6.0)
 
 
@@ -44,6 +47,9 @@ FAMILIES = {
     # shortest horizon
     "N1": (lambda: _batch((0.2, 1.0), N=1, nx=4, nu=2, Q_diag=1.0), [5, 6]),
 }
+# random stage structure (tests/soft_cases.py): the admitted draws of each case as one batch that shares sizes and idxb
+FAMILIES.update({"rs_" + c: ((lambda c=c: SC.problems(c)), SC.kks(c)) for c in SC.CASES})
+RS_ORDER = ("mixed_N4", "rs_odd", "rs_stray")  # rs_odd: two four-stage sweeps; rs_stray: stray writes into live qx
 
 
 @pytest.fixture(scope="module")
@@ -77,26 +83,32 @@ def test_batch_vs_oracle(refs, name):
     sv.ws.fill_(float("nan"))  # the workspace needs no initialisation
     sv.solve(**ARGS)
     got = sv.results()
+    for i, (sq, g, r) in enumerate(zip(sqs, got, ref)):
+        share = SC.gate_share(SC.soft_errors(sq, g, r))
+        print(f"batch {name} problem {i}: kk {g['kk']} ret {g['ret']}, share of gate " +
+              " ".join(f"{k} {v:.2e}" for k, v in share.items()))
     _check(sqs, got, ref)
-    if name == "mixed_N4":  # the waves retire at different iterations
+    if name in ("mixed_N4", "rs_odd"):  # the waves retire at different iterations
         assert len({g["kk"] for g in got}) > 1
 
 
-def test_sub_range(refs):
-    sqs, ref = refs("mixed_N4")
+@pytest.mark.parametrize("name", RS_ORDER)
+def test_sub_range(refs, name):
+    sqs, ref = refs(name)
+    last = len(sqs) - 1  # every problem but the first and the last: 1..3 of mixed_N4's and rs_odd's five
     sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
     for x in (sv.ux, sv.pi, sv.lam, sv.t, sv.stat):
         x.fill_(-7.25)
     sv.kk.fill_(-3)
     sv.ret.fill_(-3)
-    sv.solve(p0=1, count=3, **ARGS)
+    sv.solve(p0=1, count=last - 1, **ARGS)
     sv.torch.cuda.synchronize()
-    for p in (0, 4):
+    for p in (0, last):
         for x in (sv.ux, sv.pi, sv.lam, sv.t, sv.stat):
             assert bool((x[p] == -7.25).all())
         assert int(sv.kk[p]) == -3 and int(sv.ret[p]) == -3
     got = sv.results()
-    _check(sqs[1:4], got[1:4], ref[1:4])
+    _check(sqs[1:last], got[1:last], ref[1:last])
 
 
 def _stat_err(g, r):
@@ -136,18 +148,35 @@ def test_warm_start(refs):
     _check(sqs, sv.results(), ref)
 
 
-def test_agrees_with_single_problem_entry_point(product, refs):
+@pytest.mark.parametrize("name", RS_ORDER)
+def test_agrees_with_single_problem_entry_point(product, refs, name):
     """kk / ret of d_ip2_mpc_soft_tv per problem; the vectors to TOL_SOFT (the fused kernel may contract products
     differently, so bitwise equality is not required)."""
-    sqs, _ = refs("mixed_N4")
+    sqs, _ = refs(name)
     sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
     sv.solve(**ARGS)
     got = sv.results()
     _check(sqs, got, [product.ipm_soft(sq.copy(), **ARGS) for sq in sqs])
 
 
-def test_shared_layout_bitwise(refs):
-    sqs, _ = refs("mixed_N4")
+def _share_tail(sqs):
+    """The draws of a random-structure case differ in every stage, so they cannot share blocks as they are: stage 0
+    of each draw in front of the stages >= 1 of the first (BAbt / RSQrq; d, Z, z stay per problem).  These hybrids are
+    no admitted draws; the test that uses them compares the product with itself, bitwise."""
+    out = []
+    for sq in sqs:
+        h = sqs[0].copy()
+        h.BAbt[0], h.RSQrq[0] = sq.BAbt[0].copy(), sq.RSQrq[0].copy()
+        h.d, h.Z, h.z = [a.copy() for a in sq.d], [a.copy() for a in sq.Z], [a.copy() for a in sq.z]
+        out.append(h)
+    return out
+
+
+@pytest.mark.parametrize("name", RS_ORDER)
+def test_shared_layout_bitwise(refs, name):
+    sqs, _ = refs(name)
+    if name != "mixed_N4":
+        sqs = _share_tail(sqs)
     out = []
     for shared in (False, True):
         sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"], shared=shared)
@@ -165,6 +194,14 @@ def test_refusals():
     sq = mass_spring_soft(6, 8, 2)
     sq.ng = sq.ng.copy()
     sq.ng[3] = 1
+    plan, err = soft_plan_create(sq)
+    assert plan is None and err == EUNSUPPORTED
+
+
+def test_refuses_stray_write_into_zl():
+    """The reference's soft-gradient write of stage N would land in Zl_N, which the same pass reads later."""
+    sq = SC.refusal_shape()
+    assert SC.soft_stray_targets(sq)[1]
     plan, err = soft_plan_create(sq)
     assert plan is None and err == EUNSUPPORTED
 
@@ -216,7 +253,7 @@ def test_no_constraints_leaves_outputs():
         assert bool((x == -7.25).all())
 
 
-@pytest.mark.parametrize("name", ["mixed_N4", "full_N9"])
+@pytest.mark.parametrize("name", ["mixed_N4", "full_N9", "rs_odd", "rs_full16"])
 def test_offsets_and_sizes(refs, name):
     sqs, _ = refs(name)
     sv = SoftBatchSolver(sqs, k_max=ARGS["k_max"])
