@@ -57,6 +57,14 @@ _SIG = dict(
     ocp_pack_batch="i:ppiiiipppppppp",
     ocp_ipm_batch="i:piiipppppppppidddiipppp",
     ocp_finish_batch="i:piiipppppppppppppppp",
+    ocp_soft_plan_create="p:ippppppi",
+    ocp_soft_plan_destroy="v:p",
+    ocp_soft_ipm_plan="p:p",
+    ocp_soft_sizes="i:pp",
+    ocp_soft_offsets="i:pp",
+    ocp_soft_pack_batch="i:ppiiiippppppppp",
+    ocp_soft_ipm_batch="i:piiippppppppppidddiipppp",
+    ocp_soft_finish_batch="i:piiippppppppppppppppp",
     kkt_scratch_doubles="l:p",
     kkt_new_rhs_batch="i:ppiiiippppppppppppip",
     ocp_kkt_batch="i:piiippppppppppp",

@@ -17,6 +17,9 @@ struct MatGradArgs;
 struct MatDirArgs;
 struct OcpPackArgs;
 struct OcpUnpackArgs;
+struct OcpSoftPackArgs;
+struct OcpSoftResArgs;
+struct OcpSoftUnpackArgs;
 
 extern "C" {
 // hpmpc_kernels.hip: the tile kernels (which: HkLaunch) and the compiled inner-stage class of a stage size
@@ -49,4 +52,10 @@ int hk_wide_ipm_launch(const WideIpmArgs* a, int count, int lds_doubles, hipStre
 // a->count * a->nsets sets -> outputs (with a->res: the finish, one set per problem and the residual norms)
 int hk_ocp_pack_launch(const OcpPackArgs* a, hipStream_t stream);
 int hk_ocp_unpack_launch(const OcpUnpackArgs* a, hipStream_t stream);
+// hk_ocp_soft.hip: the soft OCP front end, dense data -> lib4 and the soft layouts (a->matrices: the matrix sections
+// and the vectors, two launches; else the vectors alone), the batched d_res_mpc_soft_tv (one workgroup per problem)
+// and the iterates -> outputs (with a->res: the residual norms)
+int hk_ocp_soft_pack_launch(const OcpSoftPackArgs* a, hipStream_t stream);
+int hk_ocp_soft_res_launch(const OcpSoftResArgs* a, hipStream_t stream);
+int hk_ocp_soft_unpack_launch(const OcpSoftUnpackArgs* a, hipStream_t stream);
 }

@@ -2,9 +2,9 @@
 // carve, shared by the host files of that path: hpmpc_capi.cpp (plan, layout tables, batched API; defines the plan
 // functions and call checks below), hpmpc_capi_queue.cpp (the problem queue), hpmpc_capi_dropin.cpp (reference-named
 // hard-constraint entry points; defines the arena functions), hpmpc_capi_soft.cpp (soft-constraint IPM and residual;
-// defines the soft refusals, layout and IPM setup), hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM),
-// hpmpc_capi_ocp.cpp (the batched OCP front end) and hpmpc_capi_kkt.cpp (the batched KKT re-solve and its tangent
-// solve; through hk_ocp_plan.h).
+// defines the soft refusals, layout and IPM setup), hpmpc_capi_soft_batch.cpp (the batched soft-constraint IPM) and
+// hpmpc_capi_ocp_soft.cpp (the soft OCP front end; both through hk_soft_plan.h), hpmpc_capi_ocp.cpp (the batched OCP
+// front end) and hpmpc_capi_kkt.cpp (the batched KKT re-solve and its tangent solve; through hk_ocp_plan.h).
 #pragma once
 #include <climits>
 #include <mutex>

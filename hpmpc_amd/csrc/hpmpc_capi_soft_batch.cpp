@@ -8,20 +8,7 @@
 // layouts at the offsets of hpmpc_mi355x_soft_offsets, ux / pi with 16 doubles per stage, and a workspace:
 //   [ factor (N+1) FSTRIDE | dux dpi b q Qx qx Pb, (N+1) 16 each | dt dlam lamt tinv | flat Qx qx Zl zl | scal | ist ]
 // (the flat block in the reference's carve order with its padding, hk_soft_args.h).
-#include <memory>
-
-#include "hk_plan.h"
-
-struct hpmpc_mi355x_soft_plan {
-    std::unique_ptr<hpmpc_mi355x_plan> tile;
-    int N = 0;
-    SoftLayout L;
-    double mu_scal = 0.0;  // soft_mu_scal; 0: no constraint anywhere
-    // workspace carve (doubles)
-    long long oV16 = 0, oCv = 0, nCv = 0, oFlat = 0, oScal = 0, oIst = 0, ws = 0;
-    DevTable<SoftStage> d_st;
-    DevTable<int> d_idx;
-};
+#include "hk_soft_plan.h"
 
 extern "C" void hpmpc_mi355x_soft_plan_destroy(hpmpc_mi355x_soft_plan* S) { delete S; }
 

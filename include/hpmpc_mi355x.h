@@ -561,6 +561,92 @@ int hpmpc_mi355x_ocp_finish_batch(const hpmpc_mi355x_ocp_plan *plan, int nprob, 
                                   double *x, double *pi_out, double *lam_out, double *t_out, double *inf_norm_res,
                                   void *stream);
 
+/* ---- the OCP front end for device-resident batches of SOFT-constrained problems ----
+ * The top layer of fortran_order_d_ip_ocp_soft_tv for a batch of problems that share stage sizes and box indices and
+ * whose DENSE data are already in HBM: pack on the device, solve with hpmpc_mi355x_ipm_soft_batch's kernel, and unpack
+ * to the wrapper's outputs and residual norms, with no host copy in between.
+ *   hpmpc_mi355x_ocp_soft_pack_batch   dense A, B, b, Q, S, R, q, r, lb, ub, Z, z -> BAbt, RSQrq, d, Z, z (ux)
+ *   hpmpc_mi355x_ocp_soft_ipm_batch    d_ip2_mpc_soft_tv on the packed arrays, every iteration in one launch
+ *   hpmpc_mi355x_ocp_soft_finish_batch u, x, pi, compact lam / t, inf_norm_res of d_res_mpc_soft_tv
+ * The conventions are those of the hpmpc_mi355x_ocp_* block above: asynchronous on `stream`, no synchronisation, only
+ * problems [p0, p0+count) read or written, count = 0 returns 0, a null required pointer or a bad range returns
+ * HPMPC_MI355X_EUNSUPPORTED.
+ * Dense arrays: as in the block above (A_k .. r_k), with idxb[k] / lb_k / ub_k listing the nb[k] hard boxes, then the
+ * ns[k] soft ones (nb[k] + ns[k] entries per stage), and Z_k / z_k (2 ns[k]) = [lower ns | upper ns] the quadratic /
+ * linear slack penalties.
+ * Packed arrays: exactly what hpmpc_mi355x_ipm_soft_batch takes with hpmpc_mi355x_ocp_soft_ipm_plan's plan and a
+ * null layout; their per-problem sizes equal hpmpc_mi355x_soft_sizes' on that plan.  Placement is that of
+ * oracle/iface_oracle.py to_soft_qp: BAbt / RSQrq as hpmpc_mi355x_ocp_pack_batch builds them (S in both triangles),
+ * d_k = [lb pnb | ub pnb | ls pns | us pns] with the soft bounds read at lb_k[nb + i] / ub_k[nb + i], Z_k padded to
+ * pns per half.
+ * THE LINEAR PENALTY z.  The reference wrapper never copies z into the IPM (fortran_order_interface.c:1712-1719), and
+ * neither does fortran_order_d_ip_ocp_soft_tv here: both solve with z = 0.  In this block a NULL dense z packs zeros
+ * -- the reference wrapper's behaviour -- and a GIVEN z is packed like Z and used by the solve and the residual: a
+ * documented extension.
+ * res_ok.  The reference's soft residual reads the variable of soft constraint i of stage k at idxb[k][nu[k] + i]
+ * (d_res_ip_soft.c:107), not at idxb[k][nb[k] + i].  That read stays inside the nb[k] + ns[k] entries only if every
+ * stage k < N with ns[k] > 0 has nu[k] <= nb[k]; the plan records this as res_ok (1, else 0).  On a plan with
+ * res_ok = 0 the residual norms are refused (HPMPC_MI355X_EUNSUPPORTED, nothing launched); the finish without norms
+ * works on every plan.
+ * Outputs: u, x, pi shaped like r, q, b; lam, t per stage compact as [lo nb | up nb | 4 soft blocks of ns] (the
+ * wrapper's layout with ng = 0); inf_norm_res 4 doubles per problem = max|r_q|, max|r_b|, max|r_d|, mu over the
+ * elements the one-problem wrapper visits (maxima from 0). */
+typedef struct hpmpc_mi355x_ocp_soft_plan hpmpc_mi355x_ocp_soft_plan;
+/* index of each dense array in hpmpc_mi355x_ocp_soft_data, hpmpc_mi355x_ocp_soft_sizes and _offsets: the first ten
+ * are HPMPC_MI355X_OCP_A .. HPMPC_MI355X_OCP_ub */
+enum { HPMPC_MI355X_OCP_SOFT_Z = 10, HPMPC_MI355X_OCP_SOFT_z = 11, HPMPC_MI355X_OCP_SOFT_NARRAYS = 12 };
+typedef struct {
+    const double *ptr[HPMPC_MI355X_OCP_SOFT_NARRAYS];  /* device pointers: A, B, b, Q, S, R, q, r, lb, ub, Z, z */
+    long long stride[HPMPC_MI355X_OCP_SOFT_NARRAYS];   /* doubles between problems (0: shared by all problems) */
+} hpmpc_mi355x_ocp_soft_data;
+/* nu has N+1 entries (nu[N] is treated as 0).  NULL with hpmpc_mi355x_last_error() = HPMPC_MI355X_EUNSUPPORTED
+ * exactly where hpmpc_mi355x_soft_plan_create refuses (ng > 0 among them), and for nb[k] + ns[k] > nu[k] + nx[k]. */
+hpmpc_mi355x_ocp_soft_plan *hpmpc_mi355x_ocp_soft_plan_create(int N, const int *nx, const int *nu, const int *nb,
+                                                              const int *const *idxb, const int *ng, const int *ns,
+                                                              int row_major);
+void hpmpc_mi355x_ocp_soft_plan_destroy(hpmpc_mi355x_ocp_soft_plan *plan);
+/* the soft plan the packed arrays belong to (owned by the soft OCP plan) */
+const hpmpc_mi355x_soft_plan *hpmpc_mi355x_ocp_soft_ipm_plan(const hpmpc_mi355x_ocp_soft_plan *plan);
+/* out[HPMPC_MI355X_OCP_SOFT_NSIZES], doubles per problem: [0..11] the dense arrays (order above) | packed [12] BAbt,
+ * [13] RSQrq, [14] d, [15] Z (= z), [16] ux (= pi), [17] lam (= t), [18] ws | [19] the residual scratch of
+ * hpmpc_mi355x_ocp_soft_finish_batch | outputs [20] u (= u0), [21] x (= x0), [22] pi, [23] lam (= t),
+ * [24] inf_norm_res | [25] res_ok | [26] N */
+#define HPMPC_MI355X_OCP_SOFT_NSIZES 27
+int hpmpc_mi355x_ocp_soft_sizes(const hpmpc_mi355x_ocp_soft_plan *plan, long long *out);
+/* out[HPMPC_MI355X_OCP_SOFT_NOFFSETS * (N+1)], per stage: [0..11] the stage's block inside one problem of each dense
+ * array (the u / x / pi outputs sit at the offsets of r / q / b), [12] its lam / t output, [13] BAbt_k, [14] RSQrq_k,
+ * [15] d_k, [16] Z_k (= z_k), [17] lam_k (= t_k) inside the packed arrays */
+#define HPMPC_MI355X_OCP_SOFT_NOFFSETS 18
+int hpmpc_mi355x_ocp_soft_offsets(const hpmpc_mi355x_ocp_soft_plan *plan, long long *out);
+/* Dense -> packed.  matrices != 0 writes EVERY element of BAbt, RSQrq, d, Z and z of the problems in range, padding
+ * as zeros: the buffers need no initialisation.  matrices = 0 rewrites only the b row of BAbt_k, the r / q row of
+ * RSQrq_k, d, Z and z (the per-step update of a receding-horizon loop).  data->ptr[HPMPC_MI355X_OCP_SOFT_z] may be
+ * null: z packs as zeros (see above).  u0, x0, ux: all three given, ux_k = [u0_k | x0_k | 0..] is written for
+ * warm_start = 1; else ux is not touched. */
+int hpmpc_mi355x_ocp_soft_pack_batch(const hpmpc_mi355x_ocp_soft_plan *plan, const hpmpc_mi355x_ocp_soft_data *data,
+                                     int matrices, int nprob, int p0, int count, double *BAbt, double *RSQrq,
+                                     double *d, double *Z, double *z, const double *u0, const double *x0, double *ux,
+                                     void *stream);
+/* hpmpc_mi355x_ipm_soft_batch on the plan's soft plan with the packed default layout.  mu0 must be > 0
+ * (HPMPC_MI355X_EUNSUPPORTED otherwise): the one-problem wrapper replaces mu0 <= 0 by the problem's largest cost
+ * entry, a per-problem value, and the kernel takes one mu0 for the whole batch. */
+int hpmpc_mi355x_ocp_soft_ipm_batch(const hpmpc_mi355x_ocp_soft_plan *plan, int nprob, int p0, int count,
+                                    const double *BAbt, const double *RSQrq, const double *Z, const double *z,
+                                    const double *d, double *ux, double *pi, double *lam, double *t, double *ws,
+                                    int k_max, double mu0, double mu_tol, double alpha_min, int warm_start,
+                                    int compute_mult, int *kk, int *ret, double *stat, void *stream);
+/* The wrapper's outputs from the iterate: u, x, pi_out, lam_out and, when t_out is not null, t_out.  With a non-null
+ * inf_norm_res first d_res_mpc_soft_tv over the batch into `res` (nprob * hpmpc_mi355x_ocp_soft_sizes()[19] doubles,
+ * no initialisation needed; ws is not touched): per problem [r_q | r_b] 16 doubles per stage each, then r_d laid out
+ * like d, then r_z laid out like Z, and after the nprob images mu per problem.  A null inf_norm_res skips the
+ * residual pass and needs no res, BAbt, RSQrq, Z, z or d.  A non-null inf_norm_res on a plan with res_ok = 0 returns
+ * HPMPC_MI355X_EUNSUPPORTED and launches nothing. */
+int hpmpc_mi355x_ocp_soft_finish_batch(const hpmpc_mi355x_ocp_soft_plan *plan, int nprob, int p0, int count,
+                                       const double *BAbt, const double *RSQrq, const double *Z, const double *z,
+                                       const double *d, const double *ux, const double *pi, const double *lam,
+                                       const double *t, double *res, double *u, double *x, double *pi_out,
+                                       double *lam_out, double *t_out, double *inf_norm_res, void *stream);
+
 /* ---- the KKT re-solve for device-resident batches, many right-hand sides per factor ----
  * d_kkt_solve_new_rhs_res_mpc_hard_tv (include/mpc_solvers.h:46, mpc_solvers/d_ip2_res_hard.c:1922) on a batch: the
  * last Newton system of an IPM re-solved for new b, q / r and bounds, one Riccati solve on the persisted factor per
