@@ -65,6 +65,10 @@ _SIG = dict(
     ocp_soft_pack_batch="i:ppiiiippppppppp",
     ocp_soft_ipm_batch="i:piiippppppppppidddiipppp",
     ocp_soft_finish_batch="i:piiippppppppppppppppp",
+    soft_kkt_scratch_doubles="l:p",
+    soft_kkt_batch="i:ppiiiippppppppppppppppiip",
+    soft_kkt_ocp_work_doubles="l:p",
+    soft_kkt_ocp_batch="i:piiiippppppppppppppppppppip",
     kkt_scratch_doubles="l:p",
     kkt_new_rhs_batch="i:ppiiiippppppppppppip",
     ocp_kkt_batch="i:piiippppppppppp",

@@ -14,11 +14,12 @@ CSRC = os.path.join(ROOT, "hpmpc_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "hpmpc_amd", "lib")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("HPMPC_ARCH", "gfx950")
-SOURCES = ["hpmpc_kernels.hip", "hk_wide.hip", "hk_wide_ipm.hip", "hk_soft.hip", "hk_soft_ipm.hip", "hk_ocp.hip", "hk_ocp_soft.hip", "hk_kkt.hip", "hk_tan.hip", "hk_adj.hip", "hk_matgrad.hip", "hk_matdir.hip", "hpmpc_capi.cpp",
+SOURCES = ["hpmpc_kernels.hip", "hk_wide.hip", "hk_wide_ipm.hip", "hk_soft.hip", "hk_soft_ipm.hip", "hk_ocp.hip", "hk_ocp_soft.hip", "hk_soft_kkt.hip", "hk_kkt.hip", "hk_tan.hip", "hk_adj.hip", "hk_matgrad.hip", "hk_matdir.hip", "hpmpc_capi.cpp",
            "hpmpc_capi_queue.cpp", "hpmpc_capi_dropin.cpp", "hpmpc_capi_soft.cpp", "hpmpc_capi_soft_batch.cpp",
            "hpmpc_capi_wide.cpp", "hpmpc_capi_pcond.cpp", "hpmpc_capi_wide_ipm.cpp", "hpmpc_capi_iface.cpp",
-           "hpmpc_capi_mpc.cpp", "hpmpc_capi_ocp.cpp", "hpmpc_capi_ocp_soft.cpp", "hpmpc_capi_kkt.cpp"]
-HEADERS = ["hpmpc_api.h", "hk_ipm_body.h", "hk_prims.h", "hk_riccati.h", "hk_ipm.h", "hk_mw.h", "hpmpc_kargs.h", "hk_wide_args.h", "hk_wide_core.h", "hk_wide_host.h", "hk_pcond_plan.h", "hk_soft_args.h", "hk_soft_body.h", "hk_launch_guard.h", "hk_launch.h", "hk_host.h", "hk_plan.h", "hk_ocp_args.h", "hk_kkt_args.h", "hk_kkt_body.h", "hk_ocp_plan.h", "hk_tan_args.h", "hk_tan_body.h", "hk_ocp_place.h", "hk_kkt_launch.h", "hk_adj_args.h", "hk_adj_body.h", "hk_matgrad_args.h", "hk_matdir_args.h", "hk_ocp_elem.h", "hk_ocp_soft_args.h", "hk_soft_plan.h"]
+           "hpmpc_capi_mpc.cpp", "hpmpc_capi_ocp.cpp", "hpmpc_capi_ocp_soft.cpp", "hpmpc_capi_soft_kkt.cpp",
+           "hpmpc_capi_kkt.cpp"]
+HEADERS = ["hpmpc_api.h", "hk_ipm_body.h", "hk_prims.h", "hk_riccati.h", "hk_ipm.h", "hk_mw.h", "hpmpc_kargs.h", "hk_wide_args.h", "hk_wide_core.h", "hk_wide_host.h", "hk_pcond_plan.h", "hk_soft_args.h", "hk_soft_body.h", "hk_launch_guard.h", "hk_launch.h", "hk_host.h", "hk_plan.h", "hk_ocp_args.h", "hk_kkt_args.h", "hk_kkt_body.h", "hk_ocp_plan.h", "hk_tan_args.h", "hk_tan_body.h", "hk_ocp_place.h", "hk_kkt_launch.h", "hk_adj_args.h", "hk_adj_body.h", "hk_matgrad_args.h", "hk_matdir_args.h", "hk_ocp_elem.h", "hk_ocp_soft_args.h", "hk_soft_plan.h", "hk_ocp_soft_plan.h", "hk_soft_kkt_args.h"]
 # MFMA accumulators stay in ordinary VGPRs: the stage tile is read and written by VALU code between
 # MFMAs, and the AGPR form costs 8 v_accvgpr moves each way per MFMA group.
 KFLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form"] + os.environ.get("HK_EXTRA_FLAGS", "").split()

@@ -20,6 +20,8 @@ struct OcpUnpackArgs;
 struct OcpSoftPackArgs;
 struct OcpSoftResArgs;
 struct OcpSoftUnpackArgs;
+struct SoftKktArgs;
+struct OcpSoftKktPackArgs;
 
 extern "C" {
 // hpmpc_kernels.hip: the tile kernels (which: HkLaunch) and the compiled inner-stage class of a stage size
@@ -58,4 +60,9 @@ int hk_ocp_unpack_launch(const OcpUnpackArgs* a, hipStream_t stream);
 int hk_ocp_soft_pack_launch(const OcpSoftPackArgs* a, hipStream_t stream);
 int hk_ocp_soft_res_launch(const OcpSoftResArgs* a, hipStream_t stream);
 int hk_ocp_soft_unpack_launch(const OcpSoftUnpackArgs* a, hipStream_t stream);
+// hk_soft_kkt.hip: the batched soft KKT re-solve, with `refactor` the factor launch (one wavefront per problem), then
+// x->nrhs right-hand-side sets for each of `count` problems in one launch; and the dense vectors of a->count * a->nrhs
+// sets -> their padded vectors
+int hk_soft_kkt_launch(const KArgs* a, const SoftKktArgs* x, int count, int refactor, hipStream_t stream);
+int hk_ocp_soft_kkt_pack_launch(const OcpSoftKktPackArgs* a, hipStream_t stream);
 }

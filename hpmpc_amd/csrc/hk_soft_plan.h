@@ -1,5 +1,6 @@
 // hk_soft_plan.h -- the soft plan of the batched soft-constraint IPM, shared by hpmpc_capi_soft_batch.cpp (which
-// creates it and solves on it) and hpmpc_capi_ocp_soft.cpp (the soft OCP front end, whose plan owns one): a tile plan
+// creates it and solves on it), hpmpc_capi_soft_kkt.cpp (the soft KKT re-solve, which reads the workspace carve) and
+// hpmpc_capi_ocp_soft.cpp (the soft OCP front end, whose plan owns one, through hk_ocp_soft_plan.h): a tile plan
 // on nb + ns boxes per stage, the soft layout and the workspace carve.
 #pragma once
 #include <memory>

@@ -9,29 +9,7 @@
 // A soft OCP plan owns a soft plan -- the packed arrays are what hpmpc_mi355x_ipm_soft_batch takes with a null layout
 // -- and the device table of stage sizes, dense offsets and soft offsets (OcpSoftStage, hk_ocp_soft_args.h).  One
 // difference from the wrapper: a given z is packed and used; the wrapper (like the reference's) leaves z at zero.
-#include "hk_ocp_soft_args.h"
-#include "hk_soft_plan.h"
-
-struct hpmpc_mi355x_ocp_soft_plan {
-    std::unique_ptr<hpmpc_mi355x_soft_plan> soft;
-    int N = 0, row_major = 0, res_ok = 0;
-    std::vector<OcpSoftStage> st;
-    long long dense[OCPS_NARR] = {};           // doubles per problem of every dense array
-    long long su = 0, sx = 0, sp = 0, sl = 0;  // u, x, pi, lam / t outputs
-    long long sRes = 0;                        // hk_ocp_soft_res output per problem
-    DevTable<OcpSoftStage> d_st;
-};
-
-namespace {
-
-inline OcpOut soft_out(const hpmpc_mi355x_ocp_soft_plan* O, double* u, double* x, double* pi, double* lam, double* t) {
-    return {u, x, pi, lam, t, O->su, O->sx, O->sp, O->sl};
-}
-inline bool soft_out_ok(const OcpOut& o) {
-    return (o.su == 0 || o.u) && (o.sx == 0 || o.x) && (o.sp == 0 || o.pi) && (o.sl == 0 || o.lam);
-}
-
-}  // namespace
+#include "hk_ocp_soft_plan.h"
 
 extern "C" void hpmpc_mi355x_ocp_soft_plan_destroy(hpmpc_mi355x_ocp_soft_plan* O) { delete O; }
 

@@ -135,6 +135,24 @@ def unflatten_soft_outputs(flat, N, nx, nu, nb, ns, keys=OUT_KEYS) -> list:
     return out
 
 
+SET_KEYS = ("b", "q", "r", "lb", "ub", "z")  # the per-set vectors of hpmpc_mi355x_soft_kkt_ocp_batch
+
+
+def flatten_soft_sets(sets, order="C", keys=SET_KEYS) -> dict:
+    """Per-set vectors of the soft re-solve: ``sets[p][r]`` is an interface-form dict (at least the sizes and ``keys``)
+    of problem p's set r -> {key: (nprob, nrhs, size) float64}, each set flattened as flatten_soft_problems does."""
+    per = [flatten_soft_problems(row, order, keys) for row in sets]
+    return {key: np.stack([f[key] for f in per]) for key in keys}
+
+
+def unflatten_soft_set_outputs(flat, N, nx, nu, nb, ns, keys=OUT_KEYS) -> list:
+    """{key: (nprob, nrhs, size)} of the per-set outputs u, x, pi, lam, t -> ``out[p][r]``: the per-stage blocks of
+    problem p's set r, as unflatten_soft_outputs gives them per problem."""
+    nprob = len(np.asarray(flat[keys[0]]))
+    return [unflatten_soft_outputs({k: np.asarray(flat[k])[p] for k in keys}, N, nx, nu, nb, ns, keys)
+            for p in range(nprob)]
+
+
 class _OcpSoftData(C.Structure):
     _fields_ = [("ptr", C.c_void_p * len(KEYS)), ("stride", C.c_longlong * len(KEYS))]
 
@@ -283,6 +301,47 @@ class OcpSoftBatchSolver(DeviceSolver):
         if norms:
             out["inf_norm_res"] = self.inf_norm_res
         return out
+
+    def kkt_buffers(self, nrhs: int = 1) -> dict:
+        """The tensors kkt_sets(nrhs=nrhs) writes (allocated on first use, then reused): the dense outputs u, x, pi, lam,
+        t (nprob, nrhs, max(size, 1)), the packed per-set work buffer and the scratch."""
+        def make(n):
+            s, L = self.sizes, lib()
+            new = lambda m: self.torch.zeros((self.nprob, n, max(int(m), 1)), dtype=self.torch.float64, device=self.dev)
+            return dict(u=new(s["u"]), x=new(s["x"]), pi=new(s["pi_out"]), lam=new(s["lam_out"]), t=new(s["lam_out"]),
+                        work=new(L.hpmpc_mi355x_soft_kkt_ocp_work_doubles(self.plan)),
+                        scratch=new(L.hpmpc_mi355x_soft_kkt_scratch_doubles(L.hpmpc_mi355x_ocp_soft_ipm_plan(self.plan))))
+        return self._per_set("soft_kkt", nrhs, make)
+
+    def kkt_sets(self, sets, nrhs, refactor=True, p0=0, count=None) -> dict:
+        """The batched soft KKT re-solve on dense vectors (hpmpc_mi355x_soft_kkt_ocp_batch): ``nrhs`` right-hand-side
+        sets per problem against one linearisation of the packed problems.  ``sets``: {key: contiguous float64 device
+        tensor (nprob, nrhs, sizes[key])} over b, q, r, lb, ub and optionally z (missing: every set takes the packed z
+        of its problem).  refactor=True linearises at the solver's iterate (lam, t) and factorises into ws first;
+        refactor=False reads the linearisation the last iteration of solve() left in ws (kk >= 1).  Returns the dict u,
+        x, pi, lam, t of (nprob, nrhs, size) device tensors -- those of kkt_buffers(nrhs), overwritten by the next call.
+        Neither the packed data nor the solver's iterate is written; ws only with refactor.  Asynchronous."""
+        p0, count = self._range(p0, count)
+        o = self.kkt_buffers(nrhs)
+        ins = [self._tensor(sets.get(key), (self.nprob, nrhs, self.sizes[key]), f"set {key}",
+                            optional=key == "z" or self.sizes[key] == 0) for key in SET_KEYS]
+        base = (self.lam.data_ptr(), self.t.data_ptr()) if refactor else (None, None)
+        check(lib().hpmpc_mi355x_soft_kkt_ocp_batch(
+            self.plan, self.nprob, p0, count, nrhs, self.BAbt.data_ptr(), self.RSQrq.data_ptr(), self.Zp.data_ptr(),
+            self.zp.data_ptr(), *base, *ins, o["u"].data_ptr(), o["x"].data_ptr(), o["pi"].data_ptr(),
+            o["lam"].data_ptr(), o["t"].data_ptr(), self.ws.data_ptr(), o["work"].data_ptr(), o["scratch"].data_ptr(),
+            1 if refactor else 0, self._stream()), "hpmpc_mi355x_soft_kkt_ocp_batch")
+        s = self.sizes
+        n = dict(u=s["u"], x=s["x"], pi=s["pi_out"], lam=s["lam_out"], t=s["lam_out"])
+        return {key: o[key][..., :n[key]] for key in n}
+
+    def resolve(self, data, refactor=True) -> dict:
+        """One set per problem: the re-solve for the b, q, r, lb, ub (and z) of ``data`` ({key: (nprob, size) device
+        tensor}; its matrices are not read).  Nothing is packed into the solver's own arrays and its iterate is left
+        alone, so a finish() afterwards still returns the solve's outputs.  Returns u, x, pi, lam, t as (nprob, size)
+        tensors: the keys of finish() without kk, status and norms."""
+        sets = {key: data[key].reshape(self.nprob, 1, -1) for key in SET_KEYS if data.get(key) is not None}
+        return {key: v[:, 0] for key, v in self.kkt_sets(sets, 1, refactor=refactor).items()}
 
     def results(self, out=None) -> list:
         """finish()'s tensors on the host, one interface-form dict per problem (synchronises)."""

@@ -414,6 +414,48 @@ class SoftBatchSolver(DeviceSolver):
             compute_mult, self.kk.data_ptr(), self.ret.data_ptr(), stat.data_ptr(),
             self._stream()), "hpmpc_mi355x_ipm_soft_batch")
 
+    def kkt_buffers(self, nrhs: int = 1) -> dict:
+        """The output and scratch tensors kkt_new_rhs(nrhs=nrhs) writes (allocated on first use, then reused): ux, pi
+        (nprob, nrhs, N+1, 16), lam, t (nprob, nrhs, sizes["C"]), scratch (nprob, nrhs,
+        hpmpc_mi355x_soft_kkt_scratch_doubles)."""
+        def make(n):
+            new = lambda *shape: self.torch.zeros((self.nprob, n) + shape, dtype=self.torch.float64, device=self.dev)
+            return dict(ux=new(self.N + 1, 16), pi=new(self.N + 1, 16), lam=new(self.sizes["C"]),
+                        t=new(self.sizes["C"]), scratch=new(int(lib().hpmpc_mi355x_soft_kkt_scratch_doubles(self.plan))))
+        return self._per_set("soft_kkt", nrhs, make)
+
+    def kkt_new_rhs(self, b, q, d, z=None, nrhs=1, refactor=True, p0=0, count=None, compute_mult=1, out=None,
+                    lam0=None, t0=None):
+        """The batched soft KKT re-solve (hpmpc_mi355x_soft_kkt_batch): the affine Newton point of a linearisation for
+        ``nrhs`` right-hand-side sets per problem, one Riccati solve each.  b, q: (nprob, nrhs, N+1, 16) device tensors
+        (b in state order, q in variable order [r | q]); d: (nprob, nrhs, sizes["d"]); z: (nprob, nrhs, sizes["Z"]) or
+        None for the problem's own z.  refactor=True linearises at (lam0, t0) -- default: the solver's iterate lam, t --
+        and factorises into ws first; refactor=False reads the linearisation the last iteration of solve() left in ws
+        (kk >= 1).  Returns ux, pi (nprob, nrhs, N+1, 16) and lam, t (nprob, nrhs, sizes["C"]): the tensors of ``out``
+        (default: kkt_buffers(nrhs), overwritten by the next call).  The problem data and the solver's iterate are not
+        written; ws only with refactor.  Asynchronous on torch's current stream."""
+        import ctypes as C
+
+        p0, count = self._range(p0, count)
+        out = self.kkt_buffers(nrhs) if out is None else out
+        P, n1, sz = self.nprob, self.N + 1, self.sizes
+        ins = [self._tensor(x, shape, name, opt) for name, x, shape, opt in (
+            ("b", b, (P, nrhs, n1, 16), False), ("q", q, (P, nrhs, n1, 16), False), ("d", d, (P, nrhs, sz["d"]), False),
+            ("z", z, (P, nrhs, sz["Z"]), True))]
+        base = [None, None]
+        if refactor:
+            base = [self._tensor(self.lam if lam0 is None else lam0, (P, sz["C"]), "lam0"),
+                    self._tensor(self.t if t0 is None else t0, (P, sz["C"]), "t0")]
+        for name, shape in (("ux", (P, nrhs, n1, 16)), ("pi", (P, nrhs, n1, 16)), ("lam", (P, nrhs, sz["C"])),
+                            ("t", (P, nrhs, sz["C"]))):
+            self._tensor(out[name], shape, f"out[{name!r}]")
+        check(lib().hpmpc_mi355x_soft_kkt_batch(
+            self.plan, C.byref(self.layout), P, p0, count, nrhs, self.BAbt.data_ptr(), self.RSQrq.data_ptr(),
+            self.Z.data_ptr(), self.z.data_ptr(), *base, *ins, out["ux"].data_ptr(), out["pi"].data_ptr(),
+            out["lam"].data_ptr(), out["t"].data_ptr(), self.ws.data_ptr(), out["scratch"].data_ptr(),
+            1 if refactor else 0, compute_mult, self._stream()), "hpmpc_mi355x_soft_kkt_batch")
+        return out["ux"], out["pi"], out["lam"], out["t"]
+
     def results(self) -> list:
         """Synchronise and return the per-problem dicts of unpack_soft_solution."""
         self.torch.cuda.synchronize(self.dev)

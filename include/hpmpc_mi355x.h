@@ -696,6 +696,65 @@ int hpmpc_mi355x_ocp_unpack_sets(const hpmpc_mi355x_ocp_plan *plan, int nprob, i
                                  const double *t, double *u, double *x, double *pi_out, double *lam_out,
                                  double *t_out, void *stream);
 
+/* ---- the KKT re-solve for device-resident batches of SOFT-constrained problems, many sets per factor ----
+ * The soft counterpart of hpmpc_mi355x_kkt_new_rhs_batch: after one hpmpc_mi355x_ipm_soft_batch the Newton system of a
+ * linearisation re-solved for new b, q / r, bounds and linear penalties z, one Riccati solve on the factor per
+ * right-hand-side set.  AN EXTENSION: the reference has no d_kkt_solve_new_rhs_* for d_ip2_mpc_soft_tv, so the call is
+ * defined here.  Layouts are those of hpmpc_mi355x_ipm_soft_batch (lam, t = [lo pnb | up pnb | s0 s1 s2 s3, pns each],
+ * d = [lb | ub | ls | us], Z, z = [lower | upper], idxb[k] the hard boxes then the soft ones).
+ * A linearisation is a pair (Lam, tau) in the layout of lam -- Lam = lam / t at some iterate, tau that iterate's t --
+ * with Zl and the Riccati factor of RSQrq_k + diag(Qx_k), both built from Lam and Z alone as the soft IPM's Hessian
+ * update builds them.  For one set (b', q' = [r' | q'], d', z') the result is the affine (sigma mu = 0) Newton point
+ * (ux', pi', lam', t'), the unique solution of
+ *   hard box j on v = idxb[j]:        t'_lo = ux'_v - lb',  t'_up = ub' - ux'_v
+ *   soft box i on v = idxb[nb + i]:   t'_0 = ux'_v - ls' + s_l,  t'_1 = us' - ux'_v + s_u,  t'_2 = s_l,  t'_3 = s_u
+ *   every multiplier:                 lam' = Lam (tau - t')    (complementarity linearised with the frozen ratio Lam)
+ *   slack stationarity:               Z_l s_l + z'_l - lam'_0 - lam'_2 = 0,  Z_u s_u + z'_u - lam'_1 - lam'_3 = 0
+ *   stationarity in ux and the dynamics with b', in the sign conventions of d_res_mpc_soft_tv
+ * so that r_q = r_b = r_d = r_z = 0 on the set's own data, with the variable of soft box i read at idxb[k][nb + i]
+ * (where the IPM puts it) and its multipliers entering r_q as lam_0 - lam_1 on every stage.  No step length is taken
+ * and no positivity is enforced, as in the hard re-solve.
+ * refactor = 0: the linearisation a solve left.  After hpmpc_mi355x_ipm_soft_batch / hpmpc_mi355x_ocp_soft_ipm_batch
+ * with kk >= 1, ws holds lam / t, 1 / t, Zl and the factor of the last iteration, all taken at iterate kk - 1; the call
+ * takes Lam = lam / t and tau = 1 / (1 / t) from there and only READS ws, so any number of re-solves may follow one
+ * solve.  After kk = 0 the result is undefined, as for the hard call.  lam0 and t0 are not read.
+ * refactor = 1: at a given iterate.  lam0, t0 (per problem, positive on the live slots; normally the iterate the solve
+ * returned) are required; a first launch, one wavefront per problem, writes 1 / t, lam / t, Qx and Zl into ws and
+ * factorises, then the sets follow.  ws needs no initialisation for this, and a later refactor = 0 call reuses it.
+ * Per set, nprob * nrhs of each (set s = p * nrhs + r belongs to problem p): b 16 doubles per stage in state order, q 16
+ * per stage in variable order [r_k | q_k], d and z in the soft layouts (hpmpc_mi355x_soft_sizes [0], [1]); the outputs ux,
+ * pi 16 per stage and lam, t in the soft layout ([2]); only live entries are written.  z null: every set takes its
+ * problem's z0.  Z and z0 are per problem (Z, and one of z / z0, are required when the plan has soft boxes).  scratch:
+ * nprob * nrhs * hpmpc_mi355x_soft_kkt_scratch_doubles(plan) doubles, no initialisation needed.  compute_mult = 0 skips
+ * pi (not written).  BAbt / RSQrq follow `lay` as in hpmpc_mi355x_ipm_soft_batch (NULL: the packed default; shared
+ * blocks allowed).  Asynchronous on `stream`; synchronises with nothing.  Only the sets of problems [p0, p0+count) are
+ * read or written; count = 0 returns 0.  nrhs < 1, a bad range, a null required pointer, a refused launch or a plan with
+ * no constraint on any stage (such problems have the ric_*_batch calls) return HPMPC_MI355X_EUNSUPPORTED and write
+ * nothing. */
+/* doubles of scratch per right-hand-side set */
+long long hpmpc_mi355x_soft_kkt_scratch_doubles(const hpmpc_mi355x_soft_plan *plan);
+int hpmpc_mi355x_soft_kkt_batch(const hpmpc_mi355x_soft_plan *plan, const hpmpc_mi355x_layout *lay, int nprob, int p0,
+                                int count, int nrhs, const double *BAbt, const double *RSQrq, const double *Z,
+                                const double *z0, const double *lam0, const double *t0, const double *b,
+                                const double *q, const double *d, const double *z, double *ux, double *pi, double *lam,
+                                double *t, double *ws, double *scratch, int refactor, int compute_mult, void *stream);
+/* The same on the dense vectors of the soft OCP front end, on the packed default layout (BAbt, RSQrq, Z, z0: the packed
+ * arrays of hpmpc_mi355x_ocp_soft_pack_batch; lam0, t0: the packed iterate; ws: the solve's).  b, q, r, lb, ub and
+ * optionally z are (nprob, nrhs, size) with the sizes hpmpc_mi355x_ocp_soft_sizes reports at [2], [6], [7], [8], [9],
+ * [11]; a null z gives every set its problem's z0.  Three launches: a vector pack per set (the placement of
+ * hpmpc_mi355x_ocp_soft_pack_batch), the call above with compute_mult = 1, and an unpack per set into u, x, pi_out,
+ * lam_out, t_out (t_out may be null), all (nprob, nrhs, size) with the sizes at [20..23], lam / t compact as
+ * [lo nb | up nb | 4 soft blocks of ns].  work: nprob * nrhs * hpmpc_mi355x_soft_kkt_ocp_work_doubles(plan) doubles for
+ * the packed per-set vectors, scratch: nprob * nrhs * hpmpc_mi355x_soft_kkt_scratch_doubles(the plan's soft plan); neither
+ * needs initialisation.  No residual norms per set.  Refusals as above, every check before the first launch. */
+long long hpmpc_mi355x_soft_kkt_ocp_work_doubles(const hpmpc_mi355x_ocp_soft_plan *plan);
+int hpmpc_mi355x_soft_kkt_ocp_batch(const hpmpc_mi355x_ocp_soft_plan *plan, int nprob, int p0, int count, int nrhs,
+                                    const double *BAbt, const double *RSQrq, const double *Z, const double *z0,
+                                    const double *lam0, const double *t0, const double *b, const double *q,
+                                    const double *r, const double *lb, const double *ub, const double *z, double *u,
+                                    double *x, double *pi_out, double *lam_out, double *t_out, double *ws, double *work,
+                                    double *scratch, int refactor, void *stream);
+
 /* ---- the KKT tangent solve: forward sensitivities of the re-solve, one set per parameter direction ----
  * The re-solve above is an affine map of (b, q, d): the factor is fixed, the step length is 1 and there is no line
  * search.  This call computes its linear part T directly,
